@@ -9,10 +9,14 @@ synthetic z-scored [B, 63] pose vectors: in-kernel perturbation (t ~ U, z ~ N), 
 DSM loss, full backward into the flat fp32 gradient, RCCL all-reduce (N > 1), global-norm clip +
 Adam + EMA.  The global batch is fixed as N grows ("B = 65536 @ 1/2/4/8 GPU") => strong scaling
 (`--per-gpu-batch 65536` keeps the per-GPU batch instead and reports "scaling": "weak").
-Rank 0 prints ONE JSON line; besides the contract's keys it carries
+Rank 0 prints ONE JSON line with the contract's keys.  A plain run sets up, warms up, times the `--steps` steps and prints it
+(`roofline` and `cpu_baseline` are null there).  With `--full` the line also carries
   roofline      -- live HIP-event timing of the dominant MFMA GEMM kernel over the timed region
   cpu_baseline  -- the CPU oracle (oracle/score_ref.py, torch-CPU port of the reference path) on the host cores
-  extra         -- M2 (1000-step sub-VP sampling, samples/s), M3 (SMPL-X FK joints, poses/s) and full LBS (vertices) of this run.
+  extra         -- M2 (1000-step sub-VP sampling, samples/s), M3 (SMPL-X FK joints, poses/s) and full LBS (vertices) of this run,
+                   the fp32 / bf16x3 modes, the small-batch legs and, for a multi-rank run, `dp` and `ranks`.
+`--dump-outputs DIR` writes what the last timed step left to its caller (loss, parameters, samples of the EMA shadow and Adam
+moments) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -95,6 +99,30 @@ def synthetic_poses(n, device, seed=42):
     mean, std = torch.tensor(g["stats/axis_normalize2/mean_poses"]), torch.tensor(g["stats/axis_normalize2/std_poses"])
     idx = torch.randint(0, poses.shape[0], (n,), generator=torch.Generator().manual_seed(seed))
     return ((poses[idx] - mean) / std).to(device), poses[idx].to(device)
+
+
+DUMP_SAMPLE = 1 << 20               # elements of each sampled state buffer in --dump-outputs
+
+
+def dump_outputs(path, out, model, state):
+    """What a caller of the training step holds after the last timed step: the step's loss, the updated parameters (the flat fp32
+    buffer, whole: 33 MB) and, as a fixed seeded sample of DUMP_SAMPLE positions shared by the three, the EMA shadow and the Adam
+    moments (whole, the four buffers would be 132 MB)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    flat = model.flat_params()
+    n = flat.numel()
+    idx = torch.from_numpy(np.sort(np.random.RandomState(0).permutation(n)[:min(DUMP_SAMPLE, n)])).to(flat.device)
+    arrays = {"step_loss": torch.as_tensor(out["step_loss"]).detach().reshape(1), "params": flat}
+    opt, ema = state["optimizer"], state["ema"]
+    shadow = ema.flat_shadow_for(flat) if ema is not None else None
+    if shadow is not None:
+        arrays["ema_params_sample"] = shadow[idx]
+    if getattr(opt, "_flat_m", None) is not None:
+        arrays["adam_m_sample"] = opt._flat_m[idx]
+        arrays["adam_v_sample"] = opt._flat_v[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.detach().float().cpu().numpy())
 
 
 def _host():
@@ -194,13 +222,19 @@ def main():
     ap.add_argument("--global-batch", type=int, default=GLOBAL_BATCH)
     ap.add_argument("--per-gpu-batch", type=int, default=0,
                     help="weak scaling: fix the batch per GPU (global batch = this x world size) instead of the global batch")
-    ap.add_argument("--sampler-steps", type=int, default=1000)
-    ap.add_argument("--no-extra", action="store_true", help="skip the sampler / FK measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, CPU baseline, other precisions / sizes / legs and multi-rank self-validation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--sampler-steps", type=int, default=1000, help="(--full) steps of the sampler leg")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the sampler / FK measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--no-live-roofline", action="store_true",
-                    help="no HIP events around the dominant GEMM kind inside the timed region (A/B timing of small batches)")
+                    help="(--full) no HIP events around the dominant GEMM kind inside the timed region (A/B timing of small batches)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not under a launcher: start the N ranks ourselves -- as CHILD processes of a parent that has not touched the GPU
@@ -256,31 +290,33 @@ def main():
 
     for _ in range(args.warmup):
         step_fn(state, batch)
-    # which GEMM kind dominates the step?  Decided HERE, by an untimed pass with events around every GEMM launch (two steps), not by a
-    # constant from an old profile: the kind with the largest total time is the one the timed region brackets
-    torch.cuda.synchronize()
-    _C.profile_enable(True)
-    for _ in range(2):
-        step_fn(state, batch)
-    torch.cuda.synchronize()
-    pre = _C.profile_collect()
-    _C.profile_enable(False)
     dominant_kind = FALLBACK_KIND
-    if pre:
-        dominant_name = max(pre.items(), key=lambda kv: kv[1][0])[0]
-        for kname in _C.PROFILE_EPI_KINDS:
-            if dominant_name.rstrip(">").endswith("," + kname):
-                dominant_kind = kname
+    live_roofline = args.full and not args.no_live_roofline
+    if args.full:
+        # which GEMM kind dominates the step?  Decided HERE, by an untimed pass with events around every GEMM launch (two steps), not by a
+        # constant from an old profile: the kind with the largest total time is the one the timed region brackets
+        torch.cuda.synchronize()
+        _C.profile_enable(True)
+        for _ in range(2):
+            step_fn(state, batch)
+        torch.cuda.synchronize()
+        pre = _C.profile_collect()
+        _C.profile_enable(False)
+        if pre:
+            dominant_name = max(pre.items(), key=lambda kv: kv[1][0])[0]
+            for kname in _C.PROFILE_EPI_KINDS:
+                if dominant_name.rstrip(">").endswith("," + kname):
+                    dominant_kind = kname
     ddp.barrier()
     torch.cuda.synchronize()
-    # live roofline: HIP events around the launches of the dominant GEMM kind only (bracketing all ~30 GEMM launches of a
+    # live roofline (--full): HIP events around the launches of the dominant GEMM kind only (bracketing all ~30 GEMM launches of a
     # step costs ~3 % of it; the full per-kind table comes from three extra, untimed steps below)
-    if ddp.dp_active():
+    if args.full and ddp.dp_active():
         ddp.stats_enable(True)
     t0 = time.perf_counter()
     for i in range(args.steps):
         # ... and only in every 4th step: the two event records per launch keep dependent kernels ~10 us apart
-        if args.no_live_roofline:
+        if not live_roofline:
             pass
         elif i % 4 == 0:
             _C.profile_enable(True, only=dominant_kind)
@@ -290,16 +326,20 @@ def main():
     torch.cuda.synchronize()
     ddp.barrier()
     elapsed = time.perf_counter() - t0
-    dp_stats = ddp.stats_collect() if ddp.dp_active() else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model, state)
+    dp_stats = ddp.stats_collect() if args.full and ddp.dp_active() else None
     ddp.stats_enable(False)
-    prof = _C.profile_collect()
-    _C.profile_enable(False)
-    _C.profile_enable(True)
-    for _ in range(3):
-        step_fn(state, batch)
-    torch.cuda.synchronize()
-    prof_all = _C.profile_collect()
-    _C.profile_enable(False)
+    prof, prof_all = {}, {}
+    if args.full:
+        prof = _C.profile_collect()
+        _C.profile_enable(False)
+        _C.profile_enable(True)
+        for _ in range(3):
+            step_fn(state, batch)
+        torch.cuda.synchronize()
+        prof_all = _C.profile_collect()
+        _C.profile_enable(False)
     loss = float(out["step_loss"])
     own_elapsed = elapsed
     if world > 1:
@@ -357,12 +397,13 @@ def main():
                         backend=torch.distributed.get_backend(), world=world,
                         note="bucket collectives are enqueued from inside the backward call as their ranges become final "
                              "(dposer_dsm_loss_fwd_bwd_notify -> StreamedAllReduce); the dead pre_dense_cond range belongs to no bucket")
-    extra = {"train_loss_last_step": loss, "nonfinite_gradient_steps_dropped": dropped, "train_tflops_algorithmic": 42.59e6 * value / 1e12,
-             "gemm_kernels": kernels}
+    extra = {"train_loss_last_step": loss, "nonfinite_gradient_steps_dropped": dropped, "train_tflops_algorithmic": 42.59e6 * value / 1e12}
+    if args.full:
+        extra["gemm_kernels"] = kernels
     if dp_extra:
         extra["dp"] = dp_extra
     per_rank = None
-    if ddp.is_initialized():
+    if args.full and ddp.is_initialized():
         # ---- self-validation of a multi-rank run (the first 8-GPU run has nobody to debug it): what the communicator says about itself,
         # which device every rank really ran on, every rank's own step time, and the N = 1 step of THIS build on every rank's GPU (global
         # batch, no collective: comparable with the single-GPU BENCH line; a slow GPU or a rank that shares a device shows up here)
@@ -404,7 +445,8 @@ def main():
                           "n1_same_build": {"what": "the single-process step (no collective) of this build at the GLOBAL batch, timed on every rank's own GPU",
                                             "ms_per_step_per_rank": [r["n1_same_build"]["ms_per_step"] if r["n1_same_build"] else None for r in per_rank],
                                             "poses_per_s_rank0": per_rank[0]["n1_same_build"]["poses_per_s"] if per_rank[0]["n1_same_build"] else None}}
-    if not args.no_extra and args.precision != "fp32":
+    extra_legs = args.full and not args.no_extra
+    if extra_legs and args.precision != "fp32":
         # the same step in fp32 parity mode (exact-fp32 MFMA, 1/16 of the bf16 matrix rate): the mode the tight parity numbers
         # of the test suite come from, next to the bf16 headline
         model.precision = "fp32"
@@ -482,7 +524,7 @@ def main():
         model.precision = args.precision
         model._engines.pop("bf16x3", None)
         torch.cuda.empty_cache()
-    if not args.no_extra:
+    if extra_legs:
         # ---- M2: 1000-step Euler-Maruyama sampling of the local shard, no trajectory kept ----
         model.eval()
         sde_s = sde_lib.subVPSDE(beta_min=cfg.model.beta_min, beta_max=cfg.model.beta_max, N=args.sampler_steps)
@@ -685,7 +727,7 @@ def main():
         extra["lbs_full_fwd_bwd_through_loss_backward"] = {"ms_mean_of_runs": sum(secs) / len(secs) * 1e3, "runs_ms": [round(x * 1e3, 4) for x in secs],
                                                            "poses_per_s_per_gpu": nl / (sum(secs) / len(secs)), "batch": nl}
 
-    if not args.no_extra and world == 1 and args.precision == "bf16":
+    if extra_legs and world == 1 and args.precision == "bf16":
         # ---- the latency-bound end of the same path (not the headline): the training step at the reference's own batch (1280 poses,
         # configs/default_amass_configs.py:22) and at the per-rank batch of the headline's 8-GPU leg (8192), BASELINE config 3 (1000-step sampler,
         # 500 poses).  Same model / optimizer state / kernels, other tilings (128x32 / 128x64 / 128x128); HBM-resident inputs, whole-call wall time.
@@ -716,7 +758,7 @@ def main():
         e = time.perf_counter() - t1
         small["sampler_500x1000"] = {"seconds": e, "samples_per_s": 500 / e, "us_per_step": e / 1000 * 1e6, "finite": bool(torch.isfinite(x3).all())}
         extra["small_batches"] = small
-    if ddp.is_initialized() and not args.no_extra:
+    if extra_legs and ddp.is_initialized():
         # the legs that shard with no collective, as every rank measured them on its own shard / GPU
         legs = [None] * torch.distributed.get_world_size()
         torch.distributed.all_gather_object(legs, {"rank": rank, "sampler_seconds": t_s_own, "sampler_samples": B_local,
@@ -724,7 +766,7 @@ def main():
                                                    "lbs_fwd_bwd_ms": extra["lbs_full_fwd_bwd"]["ms"]})
         extra["ranks"]["unsharded_legs_per_rank"] = legs
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:

@@ -232,7 +232,7 @@ def test_bench_runs_as_two_ranks_launched_by_torchrun():
     env = dict(os.environ, DPOSER_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", DPOSER_BENCH_N1_LEG="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--global-batch", "8192", "--no-extra", "--no-cpu-baseline"]
+           "--global-batch", "8192", "--full", "--no-extra", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -277,7 +277,7 @@ def test_bench_attributes_the_step_of_a_forced_one_rank_rccl_group():
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                DPOSER_DIST_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--global-batch", "8192",
-                        "--no-extra", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-extra", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     dp = j["extra"]["dp"]

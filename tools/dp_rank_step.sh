@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd $R
-COMMON="--no-extra --no-cpu-baseline --no-live-roofline --steps 200 --warmup 20"
+COMMON="--full --no-extra --no-cpu-baseline --no-live-roofline --steps 200 --warmup 20"
 {
 echo "# per-rank data-parallel step on one MI355X ($TAG, $(git -C $R rev-parse --short HEAD 2>/dev/null || cat $R/.head_rev 2>/dev/null || echo snapshot))"
 echo
