@@ -64,6 +64,27 @@ class LbsJointFold(C.Structure):
                 ("entry_weight", C.c_void_p), ("n_slots", C.c_int32)]
 
 
+class SmplifyArgs(C.Structure):
+    """dposer_smplify_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("net", C.c_void_p), ("flat_params", C.c_void_p), ("packed", C.c_void_p), ("net_ws", C.c_void_p), ("sde", C.POINTER(SdeDesc)),
+                ("freq", C.c_void_p), ("sigmas", C.c_void_p), ("body", C.c_void_p), ("lbs_ws_fwd", C.c_void_p), ("lbs_ws_bwd", C.c_void_p),
+                ("posedirs_packed", C.c_void_p), ("posedirs_bwd_packed", C.c_void_p), ("v_template", C.c_void_p), ("shapedirs", C.c_void_p),
+                ("j_template", C.c_void_p), ("jdirs", C.c_void_p), ("skin_idx", C.c_void_p), ("skin_w", C.c_void_p), ("skin_k", C.c_int32),
+                ("joint_ptr", C.c_void_p), ("joint_vidx", C.c_void_p), ("joint_w", C.c_void_p), ("extra_vertex_ids", C.c_void_p),
+                ("fold", C.POINTER(LbsJointFold)), ("segment_joints_host", C.POINTER(C.c_int32)), ("num_segments", C.c_int32),
+                ("orient_segment", C.c_int32), ("body_segment", C.c_int32), ("num_vertices", C.c_int32), ("num_joints", C.c_int32),
+                ("joint_rows", C.c_int32), ("num_shape", C.c_int32), ("num_betas", C.c_int32), ("batch", C.c_int64), ("row0", C.c_int64),
+                ("inv_batch", C.c_float), ("n_keypoints", C.c_int32), ("joint_map", C.c_void_p), ("map_ptr", C.c_void_p), ("map_entry", C.c_void_p),
+                ("op_joints", C.c_int32 * 4), ("gt_joints", C.c_int32 * 4), ("ign_joints", C.c_int32 * 8), ("n_ign", C.c_int32),
+                ("keypoints", C.c_void_p), ("focal_length", C.c_void_p), ("camera_center", C.c_void_p), ("cam_t_est", C.c_void_p),
+                ("global_orient", C.c_void_p), ("body_pose", C.c_void_p), ("shape", C.c_void_p), ("cam_t", C.c_void_p), ("norm_mode", C.c_int32),
+                ("norm_a", C.c_void_p), ("norm_b", C.c_void_p), ("rot6d", C.c_int32), ("num_iters", C.c_int32), ("n_stages", C.c_int32),
+                ("t_host", C.POINTER(C.c_float)), ("w_pose_host", C.POINTER(C.c_float)), ("w_shape_host", C.POINTER(C.c_float)),
+                ("w_angle_host", C.POINTER(C.c_float)), ("sigma", C.c_float), ("depth_weight", C.c_float), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("seed", C.c_uint64), ("step0", C.c_uint32), ("noise", C.c_void_p), ("scratch", C.c_void_p),
+                ("loss_log", C.c_void_p), ("reprojection", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -105,6 +126,8 @@ SIGNATURES = {
                                              C.POINTER(f32), C.POINTER(f32), i32, f64, f64, f64, f64, vp, u64, u32, vp, vp, i64, vp]),
     "dposer_motion_denoise_scratch_bytes": (i64, [i64, i32, i32, i32]),
     "dposer_motion_denoise_optimize": (C.c_int, [C.POINTER(MotionDenoiseArgs), vp]),
+    "dposer_smplify_scratch_bytes": (i64, [i64, i32, i32, i32, i32, i32]),
+    "dposer_smplify_optimize": (C.c_int, [C.POINTER(SmplifyArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),
     "dposer_dsm_loss_fwd_bwd_bucketed": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,

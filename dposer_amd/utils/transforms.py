@@ -65,3 +65,20 @@ def rotmat_to_axis_angle(R):
 def rot6d_to_axis_angle(rot6d):
     """transforms.py:197-224 (Gram-Schmidt + matrix -> axis-angle + NaN -> 0) in one HIP kernel."""
     return _launch_to_aa("dposer_rot6d_to_axis_angle", rot6d, 6)
+
+
+def cam_crop2full(crop_cam, center, scale, full_img_shape, focal_length):
+    """Weak-perspective crop camera (s, tx, ty) [N, 3] -> full-image translation (tx, ty, tz) [N, 3] (transforms.py:172-190).
+    ``center`` [N, 2] bbox centre, ``scale`` [N] bbox size / 200, ``full_img_shape`` [N, 2] (height, width), ``focal_length`` [N]
+    or scalar.  Host-side helper of run/fitting.py: builds SMPLify's ``init_cam_t``."""
+    img_h, img_w = full_img_shape[:, 0], full_img_shape[:, 1]
+    bs = scale * 200 * crop_cam[:, 0] + 1e-9
+    tz = 2 * focal_length / bs
+    tx = 2 * (center[:, 0] - img_w / 2.) / bs + crop_cam[:, 1]
+    ty = 2 * (center[:, 1] - img_h / 2.) / bs + crop_cam[:, 2]
+    return torch.stack([tx, ty, tz], dim=-1)
+
+
+def estimate_focal_length(img_h, img_w):
+    """Focal length of a ~55 degree field of view: the image diagonal (transforms.py:193-194)."""
+    return (img_w * img_w + img_h * img_h) ** 0.5

@@ -595,6 +595,105 @@ typedef struct dposer_motion_denoise_args {
 int64_t dposer_motion_denoise_scratch_bytes(int64_t frames, int32_t pose_dim, int32_t num_vertices, int32_t joint_rows);
 int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* args, void* stream);
 
+/* SMPLify -- run/smplify.py:118-281 (SMPLify.__call__; losses lib/body_model/fitting_losses.py:57-131): B independent fits of SMPL-X to
+ * 2D keypoints, all num_iters + n_stages * num_iters torch.optim.Adam iterations queued from one call:
+ *   camera stage (:200-222): Adam over [global_orient | cam_t] on camera_fitting_loss (sum over the batch: OP hips / shoulders, or the
+ *     four GT joints for an image whose OP confidences are not all > 0, plus depth_weight^2 (t_z - t_z_est)^2);
+ *   confidences of ign_joints zeroed in `keypoints` (:238);
+ *   body stage (:240-263): a fresh Adam over [body_pose | betas | global_orient] on body_fitting_loss (mean over the batch: GMoF reprojection
+ *     with conf^2, w_pose^2 * DPoser prior (sum / batch_size at the iteration's t, weight 0.5 sqrt(1 + SNR)), w_angle^2 * angle prior,
+ *     w_shape^2 * |betas|^2) with the weights of stage s = k / num_iters (:145-149);
+ *   reprojection [B, n_keypoints] out: conf^2 * GMoF of the final parameters (:266-277).
+ * The camera translation reaches the projection only as transl of the body model (fitting_losses.py:8-38 never reads its translation).
+ * Body model: a handle whose mesh is just the vertices the mapped extra joints read (rows [num_joints, joint_rows) of the LBS joint output,
+ * vertex-selected through extra_vertex_ids, no landmarks); v_template / shapedirs [V, 3, num_shape] of those vertices, j_template / jdirs of
+ * the full asset; shape [B, num_shape]: the first num_betas columns are the betas being fitted, the rest stay as given (expression).
+ *   joint_map [n_keypoints]: LBS joint row of each keypoint; map_ptr [joint_rows + 1] / map_entry: keypoints of each row (their gradients are
+ *   summed in that order -- no atomics);  op_joints / gt_joints: keypoint indices of camera_fitting_loss (:97-100).
+ *   batch images of a larger problem of inv_batch = 1 / B_global images starting at global image row0: the prior noise is keyed by the
+ *   global image index (Philox(seed, step0 + k) when noise == NULL, else noise [n_stages * num_iters, batch, network inputs]).
+ *   t_host [n_stages * num_iters]; w_pose_host / w_shape_host / w_angle_host [n_stages]: HOST arrays.
+ *   scratch: dposer_smplify_scratch_bytes(batch, V, J, joint_rows, num_shape, network inputs) bytes, 256-byte aligned.
+ *   loss_log: DEVICE [num_iters * (1 + n_stages), batch, 4] or NULL: camera rows (camera loss, 0, 0, depth term), body rows (reprojection,
+ *   angle, shape, prior) weighted as they enter the loss; the prior entry is the batch's sum / batch_size term.
+ * Allocates nothing, never synchronises the host. */
+typedef struct dposer_smplify_args {
+    dposer_scorefc_t net;
+    const float* flat_params;
+    const void* packed;
+    void* net_ws;
+    const dposer_sde_desc* sde;
+    const float* freq;
+    const float* sigmas;
+    dposer_body_t body;
+    void* lbs_ws_fwd;
+    void* lbs_ws_bwd;
+    const void* posedirs_packed;
+    const void* posedirs_bwd_packed;
+    const float* v_template;
+    const float* shapedirs;
+    const float* j_template;
+    const float* jdirs;
+    const int32_t* skin_idx;
+    const float* skin_w;
+    int32_t skin_k;
+    const int32_t* joint_ptr;
+    const int32_t* joint_vidx;
+    const float* joint_w;
+    const int32_t* extra_vertex_ids;
+    const dposer_lbs_joint_fold* fold;
+    const int32_t* segment_joints_host;
+    int32_t num_segments;
+    int32_t orient_segment;
+    int32_t body_segment;
+    int32_t num_vertices;
+    int32_t num_joints;
+    int32_t joint_rows;
+    int32_t num_shape;
+    int32_t num_betas;
+    int64_t batch;        /* at most 65535 images per call (one grid row per pose in the skinning kernels) */
+    int64_t row0;
+    float inv_batch;
+    int32_t n_keypoints;  /* <= 64: one wave per image */
+    const int32_t* joint_map;
+    const int32_t* map_ptr;
+    const int32_t* map_entry;
+    int32_t op_joints[4];
+    int32_t gt_joints[4];
+    int32_t ign_joints[8];
+    int32_t n_ign;
+    float* keypoints;             /* [B, n_keypoints, 3] (x, y, confidence) */
+    const float* focal_length;    /* [B] */
+    const float* camera_center;   /* [B, 2] */
+    const float* cam_t_est;       /* [B, 3] */
+    float* global_orient;         /* [B, 3] */
+    float* body_pose;             /* [B, body joints * 3] */
+    float* shape;                 /* [B, num_shape] */
+    float* cam_t;                 /* [B, 3] */
+    int32_t norm_mode;
+    const float* norm_a;
+    const float* norm_b;
+    int32_t rot6d;
+    int32_t num_iters;
+    int32_t n_stages;
+    const float* t_host;
+    const float* w_pose_host;
+    const float* w_shape_host;
+    const float* w_angle_host;
+    float sigma;
+    float depth_weight;
+    double lr, beta1, beta2, eps;
+    uint64_t seed;
+    uint32_t step0;
+    const float* noise;
+    void* scratch;
+    float* loss_log;
+    float* reprojection;          /* [B, n_keypoints] */
+} dposer_smplify_args;
+int64_t dposer_smplify_scratch_bytes(int64_t batch, int32_t num_vertices, int32_t num_joints, int32_t joint_rows, int32_t num_shape,
+                                     int32_t net_inputs);
+int dposer_smplify_optimize(const dposer_smplify_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
