@@ -85,6 +85,12 @@ class SmplifyArgs(C.Structure):
                 ("loss_log", C.c_void_p), ("reprojection", C.c_void_p)]
 
 
+class MeshSiArgs(C.Structure):
+    """dposer_mesh_si_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("vertices", C.c_void_p), ("batch", C.c_int64), ("num_vertices", C.c_int32), ("faces", C.c_void_p), ("num_faces", C.c_int32),
+                ("face_order", C.c_void_p), ("flags", C.c_void_p), ("counts", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -128,6 +134,8 @@ SIGNATURES = {
     "dposer_motion_denoise_optimize": (C.c_int, [C.POINTER(MotionDenoiseArgs), vp]),
     "dposer_smplify_scratch_bytes": (i64, [i64, i32, i32, i32, i32, i32]),
     "dposer_smplify_optimize": (C.c_int, [C.POINTER(SmplifyArgs), vp]),
+    "dposer_mesh_self_intersections_scratch_bytes": (i64, [i64, i32]),
+    "dposer_mesh_self_intersections": (C.c_int, [C.POINTER(MeshSiArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),
     "dposer_dsm_loss_fwd_bwd_bucketed": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,

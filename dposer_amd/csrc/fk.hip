@@ -686,7 +686,11 @@ static BodyTuning& body_tuning() {
     static BodyTuning t = [] { BodyTuning x; x.load(); return x; }();
     return t;
 }
-extern "C" void dposer_body_tuning_reload(void) { body_tuning().load(); }
+void meshsi_tuning_reload();      // meshsi.hip: its switch (DPOSER_SI_ALLPAIRS) is re-read with the body-model ones
+extern "C" void dposer_body_tuning_reload(void) {
+    body_tuning().load();
+    meshsi_tuning_reload();
+}
 static int64_t fk_small_max() { return body_tuning().fk_small_max; }
 
 template <typename Kin> __global__ void __launch_bounds__(64) k_fk_small(FkArgs a) {

@@ -694,6 +694,36 @@ int64_t dposer_smplify_scratch_bytes(int64_t batch, int32_t num_vertices, int32_
                                      int32_t net_inputs);
 int dposer_smplify_optimize(const dposer_smplify_args* args, void* stream);
 
+/* Mesh self-intersections -- the SI metric of run/demo.py:148-161 (lib/utils/metric.py:41-92 delegates to PyMeshLab's
+ * compute_selection_by_self_intersections_per_face): for B meshes sharing one face list, which faces intersect another face of their mesh.
+ * Pair rule, from the vertex INDICES of faces f != g (a face with a repeated index is degenerate: never tested, never flagged):
+ *   3 shared indices (duplicate face): intersect;  2 (an edge): do not;
+ *   1 shared vertex s: with a, b f's other two vertices, the segment (s+a)/2 -> (s+b)/2 crosses g at a point strictly inside g (barycentric
+ *     (b1, b2) on g's 2nd / 3rd vertex: b1 > 1e-6, b2 > 1e-6, b1 + b2 < 1; the segment's ends count), or the same with f and g swapped;
+ *   0 shared: Moller's triangle-triangle test with its coplanar branch, touching counts as intersecting.
+ * Pairs whose bounding boxes do not meet (closed boxes) are not tested.  The 0-shared test runs with the pair in a fixed order (sorted vertex
+ * indices, lexicographic), so the flags do not depend on the order of the faces, the tiling or the schedule.  All arithmetic fp32.
+ *   vertices [batch, num_vertices, 3];  faces [num_faces, 3] int32, indices in [0, num_vertices) (not checked: device data);
+ *   face_order [num_faces]: a permutation of the faces that makes runs of 64 consecutive faces compact surface patches (only the speed of the
+ *     tile culling depends on it), or NULL for the identity;
+ *   flags [batch, num_faces] out: 1 where the face intersects another face of its mesh, else 0;  counts [batch] out: flagged faces per mesh;
+ *   scratch: dposer_mesh_self_intersections_scratch_bytes(batch, num_faces) bytes, 256-byte aligned.
+ * DPOSER_SI_ALLPAIRS=1 (read once per process, dposer_body_tuning_reload re-reads it): every tile pair is walked, no tile culling -- the
+ * cross-check that culling changes no flag.  Allocates nothing, never synchronises the host. */
+typedef struct dposer_mesh_si_args {
+    const float* vertices;
+    int64_t batch;
+    int32_t num_vertices;
+    const int32_t* faces;
+    int32_t num_faces;
+    const int32_t* face_order;
+    uint8_t* flags;
+    int32_t* counts;
+    void* scratch;
+} dposer_mesh_si_args;
+int64_t dposer_mesh_self_intersections_scratch_bytes(int64_t batch, int32_t num_faces);
+int dposer_mesh_self_intersections(const dposer_mesh_si_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
