@@ -91,6 +91,20 @@ class MeshSiArgs(C.Structure):
                 ("face_order", C.c_void_p), ("flags", C.c_void_p), ("counts", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1
+
+
+class RenderArgs(C.Structure):
+    """dposer_render_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("vertices", C.c_void_p), ("num_meshes", C.c_int64), ("num_vertices", C.c_int32), ("faces", C.c_void_p),
+                ("num_faces", C.c_int32), ("transforms", C.c_void_p), ("image_of_mesh", C.c_void_p), ("num_images", C.c_int64),
+                ("height", C.c_int32), ("width", C.c_int32), ("intrinsics", C.c_void_p), ("znear", C.c_float), ("zfar", C.c_float),
+                ("base_color", C.c_void_p), ("lights", C.c_void_p), ("num_lights", C.c_int32), ("ambient", C.c_float * 3),
+                ("smooth", C.c_int32), ("vf_ptr", C.c_void_p), ("vf_face", C.c_void_p), ("background", C.c_void_p),
+                ("background_stride", C.c_int64), ("background_color", C.c_uint8 * 4), ("rgb", C.c_void_p), ("depth", C.c_void_p),
+                ("face_id", C.c_void_p), ("mesh_id", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -135,6 +149,8 @@ SIGNATURES = {
     "dposer_smplify_scratch_bytes": (i64, [i64, i32, i32, i32, i32, i32]),
     "dposer_smplify_optimize": (C.c_int, [C.POINTER(SmplifyArgs), vp]),
     "dposer_mesh_self_intersections_scratch_bytes": (i64, [i64, i32]),
+    "dposer_render_scratch_bytes": (i64, [i64, i32, i32, i64, i32, i32]),
+    "dposer_render_meshes": (C.c_int, [C.POINTER(RenderArgs), vp]),
     "dposer_mesh_self_intersections": (C.c_int, [C.POINTER(MeshSiArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),

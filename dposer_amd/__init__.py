@@ -30,6 +30,7 @@ _ALIASES = {
     "lib.body_model.smpl": "dposer_amd.body_model.smpl",
     "lib.body_model.utils": "dposer_amd.body_model.utils",
     "lib.body_model.constants": "dposer_amd.body_model.constants",
+    "lib.body_model.visual": "dposer_amd.body_model.visual",
     "lib.utils": "dposer_amd.utils",
     "lib.utils.transforms": "dposer_amd.utils.transforms",
     "lib.utils.misc": "dposer_amd.utils.misc",

@@ -724,6 +724,67 @@ typedef struct dposer_mesh_si_args {
 int64_t dposer_mesh_self_intersections_scratch_bytes(int64_t batch, int32_t num_faces);
 int dposer_mesh_self_intersections(const dposer_mesh_si_args* args, void* stream);
 
+/* Batched mesh rendering -- what lib/body_model/visual.py:132-366 does with pyrender / pytorch3d (render_mesh, multiple_render,
+ * faster_render, Renderer): B meshes sharing one face list, rasterised with a depth test into num_images images in one call.
+ * Frames: vertices are in the model frame; transforms [B, 3, 4] (row-major) take them to the camera frame, OpenCV's (x right, y down,
+ * z forward); image n projects u = fx x / z + cx, v = fy y / z + cy with intrinsics[n] = (fx, fy, cx, cy).  Pixel (row i, col j) covers
+ * [j, j+1) x [i, i+1) and is sampled at its centre (j + 0.5, i + 0.5).  Mesh b is drawn into image image_of_mesh[b] (NULL: image b);
+ * meshes of one image are depth-tested together.  Each vertex is projected exactly once per mesh.
+ * Coverage: with the projected corners of a face in its index order, each edge function is evaluated in fp32 with its endpoints in
+ *   canonical order (lower vertex index first: E = (x_hi - x_lo)(py - y_lo) - (y_hi - y_lo)(px - x_lo)) and negated as the face's winding
+ *   and the sign of its area require, so that the interior is positive.  A centre is covered when every edge value is > 0, or == 0 on an
+ *   edge that is top-left in that orientation (direction (dx, dy) with dy < 0, or dy == 0 and dx > 0).  Either winding, no culling.  Two
+ *   faces that share an edge see exactly opposite values on it, so no centre on a shared edge is missed or covered twice.
+ * Depth: perspective-correct, z = 1 / sum_i b_i / z_i with b_i the edge values normalised by their sum.  The key of a fragment is
+ *   (bits of z) << 32 | (b * num_faces + f) and the smallest key wins: the nearest fragment, ties to the lower (mesh, face), whatever the
+ *   launch order, face order or grouping.  b * num_faces + f must stay below 2^32 - 1 (checked).
+ * Dropped faces (never write anything): a corner with z <= znear (no clipping, unlike OpenGL), all corners beyond zfar (a face that
+ *   straddles zfar is drawn whole), zero area in fp32, a non-finite corner, a repeated vertex index.
+ * Shading: c = clamp(base * (ambient + sum_l I_l max(0, n . l)), 0, 1), 8-bit value rint(255 c), no specular term.  l is the unit vector
+ *   toward the light: lights[l] = (kind, x, y, z, r, g, b), kind 0 = directional (x, y, z: direction toward the light), 1 = point
+ *   (position; no attenuation), all in the camera frame.  n is the camera-frame face normal (smooth = 0), or (smooth = 1) the
+ *   perspective-correct interpolation of vertex normals, each the normalised sum of the unit normals of the faces around it (a
+ *   vertex -> face CSR built on the host, vf_ptr [V + 1] / vf_face; render_meshes orders a vertex's faces by their sorted vertex
+ *   indices, so the sum does not depend on the face order); n is turned to face the
+ *   camera at the shaded point.  Uncovered pixels take background [H, W, 3] (+ n * background_stride bytes for image n; stride 0:
+ *   shared), or background_color when background is NULL.
+ * Outputs (each optional, NULL = not written), [num_images, H, W]: rgb uint8 [.., 3]; depth fp32 (camera z, 0 where empty); face_id and
+ *   mesh_id int32 (-1 where empty).  scratch: dposer_render_scratch_bytes(...) bytes, 256-byte aligned.  faces / image_of_mesh / vf_* are
+ *   device data and not range-checked here.  Allocates nothing, never synchronises the host. */
+#define DPOSER_LIGHT_DIRECTIONAL 0
+#define DPOSER_LIGHT_POINT 1
+typedef struct dposer_render_args {
+    const float* vertices;        /* [num_meshes, num_vertices, 3] */
+    int64_t num_meshes;
+    int32_t num_vertices;
+    const int32_t* faces;         /* [num_faces, 3] */
+    int32_t num_faces;
+    const float* transforms;      /* [num_meshes, 3, 4] */
+    const int32_t* image_of_mesh; /* [num_meshes] or NULL */
+    int64_t num_images;
+    int32_t height, width;
+    const float* intrinsics;      /* [num_images, 4] */
+    float znear, zfar;
+    const float* base_color;      /* [num_meshes, 3] */
+    const float* lights;          /* [num_lights, 7] */
+    int32_t num_lights;
+    float ambient[3];
+    int32_t smooth;
+    const int32_t* vf_ptr;        /* [num_vertices + 1], smooth only */
+    const int32_t* vf_face;       /* [vf_ptr[num_vertices]], smooth only */
+    const uint8_t* background;    /* [H, W, 3] or NULL */
+    int64_t background_stride;    /* bytes between the backgrounds of consecutive images; 0 = one shared */
+    uint8_t background_color[4];  /* RGB (+ pad) where background is NULL */
+    uint8_t* rgb;
+    float* depth;
+    int32_t* face_id;
+    int32_t* mesh_id;
+    void* scratch;
+} dposer_render_args;
+int64_t dposer_render_scratch_bytes(int64_t num_meshes, int32_t num_vertices, int32_t num_faces, int64_t num_images, int32_t height,
+                                    int32_t width);
+int dposer_render_meshes(const dposer_render_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
