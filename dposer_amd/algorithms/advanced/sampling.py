@@ -8,8 +8,10 @@ configs/subvp/amass_scorefc_continuous.py:30-32) on a sub-VP/VP SDE with a Score
 ``dposer_em_sampler``: the whole N-step loop is enqueued by one C call, the time branch of the
 network collapses into a per-step bias table, the predictor update / completion imputation /
 re-tiling of x for the next step are fused into one elementwise kernel per step, and noise is
-drawn in-kernel (Philox).  Any other predictor/corrector combination runs the generic loop below on
-top of the HIP score function.
+drawn in-kernel (Philox).  With ``probability_flow=True`` (deterministic sampling along the
+probability-flow ODE, what run/demo.py's interpolation task decodes latents with) the same predictor
+runs as ``dposer_pf_sampler``: the drift's score term is halved and no noise is added or drawn.  Any
+other predictor/corrector combination runs the generic loop below on top of the HIP score function.
 """
 import abc
 import ctypes as C
@@ -253,15 +255,18 @@ def shared_corrector_update_fn(x, t, observation, mask, sde, model, corrector, c
 
 
 def fused_em_supported(sde, model, predictor, corrector, probability_flow, continuous):
+    """Euler-Maruyama + corrector 'none' on a fused SDE and a ScoreModelFC; ``probability_flow`` selects dposer_pf_sampler."""
     from .model import ScoreModelFC
-    return (predictor is EulerMaruyamaPredictor and corrector in (None, NoneCorrector) and not probability_flow
+    return (predictor is EulerMaruyamaPredictor and corrector in (None, NoneCorrector)
             and sde_lib.sde_desc(sde, continuous) is not None
             and isinstance(model, ScoreModelFC))
 
 
 def fused_em_sample(model, sde, x, timesteps, *, start_step=0, observation=None, mask=None, noise=None, seed=0,
-                    traj_stride=0, continuous=True):
-    """dposer_em_sampler.  x [B, D] initial state (consumed); returns (trajs or None, x, x_mean)."""
+                    traj_stride=0, continuous=True, probability_flow=False):
+    """dposer_em_sampler (dposer_pf_sampler with ``probability_flow``).  x [B, D] initial state (consumed); returns
+    (trajs or None, x, x_mean).  Under probability flow x == x_mean and ``noise`` keeps the stochastic layout: its predictor
+    slots are not read."""
     _C.require_gpu(x, "sampler state")
     eng = model._engine()
     flat = model.flat_params()
@@ -284,10 +289,11 @@ def fused_em_sample(model, sde, x, timesteps, *, start_step=0, observation=None,
     obs = None if observation is None else observation.contiguous().float()
     msk = None if mask is None else mask.contiguous().float()
     nz = None if noise is None else noise.contiguous().float()
-    _C.check(eng.lib.dposer_em_sampler(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), _C.ptr(x), _C.ptr(x_mean),
-                                       C.c_void_p(ts_host.data_ptr()), int(start_step), _C.ptr(obs), _C.ptr(msk), _C.ptr(nz),
-                                       int(seed), _C.ptr(traj), int(traj_stride or 1), _C.ptr(eng.freq(x.device, model._fourier_W())),
-                                       _C.ptr(model.sigmas), B, _C.stream_ptr()), "dposer_em_sampler")
+    name = "dposer_pf_sampler" if probability_flow else "dposer_em_sampler"
+    _C.check(getattr(eng.lib, name)(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), _C.ptr(x), _C.ptr(x_mean),
+                                    C.c_void_p(ts_host.data_ptr()), int(start_step), _C.ptr(obs), _C.ptr(msk), _C.ptr(nz),
+                                    int(seed), _C.ptr(traj), int(traj_stride or 1), _C.ptr(eng.freq(x.device, model._fourier_W())),
+                                    _C.ptr(model.sigmas), B, _C.stream_ptr()), name)
     return traj, x, x_mean
 
 
@@ -401,7 +407,8 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                 trajs, x, x_mean = fused_em_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), start_step=start_t,
                                                    observation=observation if completion else None,
                                                    mask=mask if completion else None, noise=noise, seed=seed,
-                                                   traj_stride=traj_stride, continuous=continuous)
+                                                   traj_stride=traj_stride, continuous=continuous,
+                                                   probability_flow=probability_flow)
                 model.train(was_training)
                 if trajs is None:
                     trajs = x.new_empty((0,) + tuple(x.shape))

@@ -314,7 +314,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_em_update(EmDev d
         f32x4 xn = {0.f, 0.f, 0.f, 0.f};
         if (s < a.B && c < a.D) {
             float zp[4], zb[4], za[4];
-            if (a.res && !a.z_pred) normals4((uint64_t)s * QD + q, STREAM_EM_NOISE, a.step, a.seed, zp);
+            if (a.res && !a.pf && !a.z_pred) normals4((uint64_t)s * QD + q, STREAM_EM_NOISE, a.step, a.seed, zp);   // (probability flow: none)
             if (a.obs && a.res && !a.z_impB) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_B, a.step, a.seed, zb);
             if (a.obs && a.t_next >= 0.f && !a.z_impA) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_A, a.step + 1, a.seed, za);
 #pragma unroll
@@ -326,12 +326,16 @@ template <typename T> __global__ void __launch_bounds__(256) k_em_update(EmDev d
                     // score = -(res / used_sigmas) / std                         model.py:194, utils.py:162
                     const float model = a.res[s * a.Cp + c + r] / usig;
                     const float score = sde_score(d.sde, model, at.sd_score);
-                    // rsde.sde: drift = -0.5 beta x - g^2 score                  sde_lib.py:98-104
+                    // rsde.sde: drift = -0.5 beta x - g^2 score (* 0.5 under probability flow)   sde_lib.py:98-104
                     float drift = (-0.5f * beta) * x;
-                    drift = drift - ((g * g) * score) * 1.0f;
+                    drift = drift - ((g * g) * score) * (a.pf ? 0.5f : 1.0f);
                     const float x_mean = x + drift * d.sde.dt;                    // sampling.py:186
-                    const float z = a.z_pred ? a.z_pred[o] : zp[r];
-                    x = x_mean + (g * d.sde.sqrt_mdt) * z;                         // sampling.py:187
+                    if (a.pf) {
+                        x = x_mean;                                                // diffusion zeros(1): sde_lib.py:104
+                    } else {
+                        const float z = a.z_pred ? a.z_pred[o] : zp[r];
+                        x = x_mean + (g * d.sde.sqrt_mdt) * z;                     // sampling.py:187
+                    }
                     a.x_mean[o] = x_mean;
                     if (a.obs) {                                                   // sampling.py:416-420 (after predictor)
                         const float m = a.mask[o];

@@ -458,8 +458,9 @@ template <typename T> struct EpiRowMajor {
 // post_dense fused with one Euler-Maruyama predictor step (sampler fast path: no observation, in-kernel noise, no trajectory).
 //   res    = acc + bias                                   model.py:189
 //   score  = -(res / used_sigma) / std(t)                 model.py:194, utils.py:162
-//   x_mean = x + (-1/2 beta x - g^2 score) * dt           sde_lib.py:98-104, sampling.py:186
+//   x_mean = x + (-1/2 beta x - g^2 score * pff) * dt     sde_lib.py:98-104, sampling.py:186   (pff = 0.5 under probability flow, else 1)
 //   x      = x_mean + g sqrt(-dt) z,  z ~ Philox          sampling.py:187
+// Probability flow (pf != 0, sde_lib.py:102-104): the diffusion is zeros(1), so x = x_mean and no normal is drawn at all.
 // The state x lives in HBM as fp32 FT [Spad][64] between steps (coalesced tile I/O; row-major only at the two ends of the
 // sampler), and the next step's network input (FT of T) is written from the same registers.  Same fp32 operation order as
 // k_em_update; the Philox counter (sample * QD + channel / 4, STREAM_EM_NOISE, step) is the one oracle/philox.py restates.
@@ -476,6 +477,7 @@ struct EmStepParams {
     int64_t S_valid;
     uint64_t seed;
     uint32_t step;
+    int pf;                // probability-flow ODE step (deterministic sampler)
 };
 template <typename T> struct EpiEmStep {
     typedef EmStepParams Params;
@@ -515,10 +517,10 @@ template <typename T> struct EpiEmStep {
                 const float model = (a[i] + (c + r < p.D ? p.bias[c + r] : 0.f)) / usig;
                 const float score = sde_score(p.sde, model, sd);
                 float drift = (-0.5f * beta) * x[i];
-                drift = drift - ((g * g) * score) * 1.0f;
+                drift = drift - ((g * g) * score) * (p.pf ? 0.5f : 1.0f);
                 const float mean = x[i] + drift * p.sde.dt;
                 xm[i] = valid ? mean : 0.f;
-                x[i] = valid ? mean + (g * p.sde.sqrt_mdt) * z[i] : 0.f;
+                x[i] = valid ? (p.pf ? mean : mean + (g * p.sde.sqrt_mdt) * z[i]) : 0.f;
             }
         }
     }
@@ -538,6 +540,7 @@ template <typename T> struct EpiEmStep {
         for (int tc = 0; tc < TC; ++tc)
 #pragma unroll
             for (int ts = 0; ts < TS; ++ts) {
+                if (p.pf) continue;                       // probability flow: no predictor normals
                 draw(p, cbase + tc * 32, sbase + ts * 32 + (lane & 31), lane >> 5, pre.z[tc * TS + ts]);
                 // (pin: without it hipcc sinks the whole draw to its first use, behind the K loop)
 #pragma unroll
@@ -575,7 +578,7 @@ template <typename T> struct EpiEmStep {
                 const int64_t tb = ft_tile_base<float>(sbase + ts * 32, c0, p.Cp);
                 float x[16], xm[16], z[16];
                 TileIO<float>::load(p.x_ft + tb, lane, x);
-                draw(p, c0, s, hi, z);
+                if (!p.pf) draw(p, c0, s, hi, z);
                 tile(p, sc, acc[tc][ts], c0, s, hi, x, xm, z);
                 TileIO<float>::store(p.x_ft + tb, lane, x);
                 if (p.x_mean_ft) TileIO<float>::store(p.x_mean_ft + tb, lane, xm);

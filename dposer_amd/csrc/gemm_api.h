@@ -63,7 +63,7 @@ struct SamplerArgs {
     int post_kblocks;
     const void* last;             // FT output of the last GroupNorm layer
     float* x_mean_ft;             // written on the last step
-    EmStepParams em;              // per-step fields (t, step, x_mean_ft) are filled in by the kernel
+    EmStepParams em;              // per-step fields (t, step, x_mean_ft) are filled in by the kernel; em.pf carries probability flow
     // cluster form only (k_sampler_cluster): all zero before the launch
     uint32_t* progress;           // DEVICE [n_sblk] tiles finished per sample block (4 per layer / update phase)
     uint32_t* ctrl;               // DEVICE [SAMPLER_CTRL_WORDS]: [0, 8) workgroups seen per XCD, [8] error flag, [9] longest wait in polls

@@ -92,7 +92,7 @@ struct EmUpdateArgs {      // EulerMaruyamaPredictor.update_fn + imputation (sam
     const float* sigmas;
     const float* obs;      // completion: observation [B][D] or null
     const float* mask;     // completion: mask [B][D]
-    const float* z_pred;   // injected predictor noise [B][D] or null (-> Philox)
+    const float* z_pred;   // injected predictor noise [B][D] or null (-> Philox); not read under probability flow
     const float* z_impB;   // injected imputation noise after the predictor, or null
     const float* z_impA;   // injected imputation noise before the NEXT predictor step, or null
     float t, t_next;       // current / next timestep (t_next < 0: last step, no look-ahead imputation)
@@ -103,6 +103,7 @@ struct EmUpdateArgs {      // EulerMaruyamaPredictor.update_fn + imputation (sam
     SdeCfg sde;
     uint64_t seed;
     uint32_t step;
+    int pf;                // probability-flow ODE step: drift factor 0.5, no diffusion, no predictor draw (sde_lib.py:102-104)
 };
 hipError_t launch_em_update(const EmUpdateArgs& a, hipStream_t st);
 // fp32 FT [Bpad][Dpad] -> row-major [B][D] (end of the fused sampler fast path); any of the two pairs may be null

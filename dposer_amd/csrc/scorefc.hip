@@ -886,13 +886,22 @@ static int build_time_table_at(dposer_scorefc_s* h, const float* flat, const cha
 static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
                            float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, const float* observation,
                            const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, const float* freq,
-                           const float* sigmas, int64_t B, void* stream);
+                           const float* sigmas, int64_t B, void* stream, int pf);
 extern "C" int dposer_em_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                  float* x, float* x_mean, const float* timesteps_host, int32_t start_step, const float* observation,
                                  const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
                                  const float* freq, const float* sigmas, int64_t B, void* stream) {
     return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, -1, observation, mask, noise, seed, traj,
-                           traj_stride, freq, sigmas, B, stream);
+                           traj_stride, freq, sigmas, B, stream, 0);
+}
+// probability_flow = True (sde_lib.py:98-105): the same loop with the drift's score term halved and no diffusion.  Same noise layout as
+// dposer_em_sampler; the predictor slots are never read, the two imputation slots of a completion call are.
+extern "C" int dposer_pf_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                 float* x, float* x_mean, const float* timesteps_host, int32_t start_step, const float* observation,
+                                 const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
+                                 const float* freq, const float* sigmas, int64_t B, void* stream) {
+    return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, -1, observation, mask, noise, seed, traj,
+                           traj_stride, freq, sigmas, B, stream, 1);
 }
 extern "C" int dposer_em_sampler_steps(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                        float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
@@ -900,13 +909,13 @@ extern "C" int dposer_em_sampler_steps(dposer_scorefc_t h, const float* flat, co
                                        int32_t traj_stride, const float* freq, const float* sigmas, int64_t B, void* stream) {
     DP_CHECK_ARG(n_steps >= 0, "n_steps must be >= 0");
     return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed, traj,
-                           traj_stride, freq, sigmas, B, stream);
+                           traj_stride, freq, sigmas, B, stream, 0);
 }
 static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
                            float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, const float* observation,
                            const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, const float* freq,
-                           const float* sigmas, int64_t B, void* stream) {
-    DpRange _dp_range("dposer_em_sampler");
+                           const float* sigmas, int64_t B, void* stream, int pf) {
+    DpRange _dp_range(pf ? "dposer_pf_sampler" : "dposer_em_sampler");
     DP_TRY(check_common(h, flat, packed_, ws_, B));
     g_alg_batch = B;
     DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
@@ -932,14 +941,15 @@ static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* pa
     std::memset(&ea, 0, sizeof(ea));
     ea.x = x; ea.x_mean = x_mean; ea.xin = w.xin; ea.sigmas = sigmas; ea.obs = observation; ea.mask = mask;
     ea.B = B; ea.Bpad = w.Bpad; ea.D = h->D; ea.Dpad = h->Dpad; ea.Cp = h->Cp; ea.num_scales = h->d.num_scales;
-    ea.f32 = h->f32; ea.scale_by_sigma = sbs_mode(h); ea.sde = sc; ea.seed = seed;
+    ea.f32 = h->f32; ea.scale_by_sigma = sbs_mode(h); ea.sde = sc; ea.seed = seed; ea.pf = pf;
     // step "-1": imputation ahead of the first predictor call (sampling.py:459) + pack x
     ea.res = nullptr; ea.t = timesteps_host[start_step]; ea.t_next = timesteps_host[start_step];
     ea.step = (uint32_t)(start_step - 1);
     ea.z_impA = (noise && observation) ? noise : nullptr;
     // Fast path (plain generation: no observation, in-kernel noise, no trajectory): the state stays in HBM as fp32 FT and
     // post_dense + the Euler-Maruyama update are ONE GEMM launch per step (EpiEmStep) -- no `res` round trip, no update kernel.
-    const bool fused = !observation && !noise && !traj && h->Cp == h->Dpad;
+    // Under probability flow the (ignored) injected predictor noise does not stand in its way.
+    const bool fused = !observation && (pf || !noise) && !traj && h->Cp == h->Dpad;
     if (fused) ea.x_ft = w.xft;
     DP_HIP_LAUNCH(launch_em_update(ea, st));
     // Persistent form of the fast path (gemm_sampler.hip): one workgroup per 256 samples walks every layer of every step -- no
@@ -980,7 +990,7 @@ static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* pa
         p.bias = flat + h->off_post_b; p.x_ft = w.xft; p.x_mean_ft = nullptr; p.xin = w.xin;
         p.sigmas = sigmas; p.sde = make_sde_dev(sc); p.t = 0.f; p.num_scales = h->d.num_scales;
         p.scale_by_sigma = sbs_mode(h); p.D = h->D; p.Cp = h->Cp; p.QD = (h->D + 3) >> 2; p.S_valid = B;
-        p.seed = seed; p.step = 0;
+        p.seed = seed; p.step = 0; p.pf = pf;     // (the persistent kernels copy these fields into every step's EpiEmStep: PF is carried)
         if (persistent_env >= 2) {
             // cluster form (gemm_sampler.hip): 2 = joined by the per-block counters, 3 = the same walk without waits (timing probe, garbage samples)
             sa.n_sblk = (int)(w.Bpad / 256);
@@ -1016,7 +1026,7 @@ static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* pa
             p.bias = flat + h->off_post_b; p.x_ft = w.xft; p.x_mean_ft = (i + 1 == n_run) ? w.xmft : nullptr; p.xin = w.xin;
             p.sigmas = sigmas; p.sde = make_sde_dev_at(sc, timesteps_host[gi]); p.t = timesteps_host[gi]; p.num_scales = h->d.num_scales;
             p.scale_by_sigma = sbs_mode(h); p.D = h->D; p.Cp = h->Cp; p.QD = (h->D + 3) >> 2; p.S_valid = B;
-            p.seed = seed; p.step = (uint32_t)gi;
+            p.seed = seed; p.step = (uint32_t)gi; p.pf = pf;
             DP_HIP_LAUNCH(gemm_em_step(gemm_prec(h), shape, g, p, st));
         }
         DP_HIP_LAUNCH(launch_ft_to_rows(w.xft, x, w.xmft, x_mean, B, w.Bpad, h->D, h->Dpad, st));

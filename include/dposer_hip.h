@@ -138,6 +138,20 @@ int dposer_em_sampler(dposer_scorefc_t h, const float* flat_params, const void* 
                       uint64_t seed, float* traj, int32_t traj_stride, const float* freq, const float* sigmas,
                       int64_t batch, void* stream);
 
+/* The same sampler with probability_flow = True: deterministic sampling along the probability-flow ODE
+ * (sampling.py:182-188 with RSDE.sde of sde_lib.py:98-105), as run/demo.py:437-450 drives it to decode ODE latents:
+ *   x_mean = x + (f(x, t) - 0.5 g(t)^2 score) dt,   x = x_mean   (the reference's diffusion is zeros(1)).
+ * Arguments and noise layout are dposer_em_sampler's, so a trace recorded from the reference maps onto the call unchanged:
+ * the predictor slot of each step is present and never read (no predictor normal is drawn); with completion the two
+ * imputation slots are read (or drawn in-kernel), since the reference imputes with randn under probability flow too
+ * (sampling.py:416-420).  Without observation and trajectory the call takes the one-launch-per-step fused form; the opt-in
+ * persistent kernels (DPOSER_SAMPLER_PERSISTENT) carry the flag as well. */
+int dposer_pf_sampler(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws,
+                      const dposer_sde_desc* sde, float* x, float* x_mean, const float* timesteps_host,
+                      int32_t start_step, const float* observation, const float* mask, const float* noise,
+                      uint64_t seed, float* traj, int32_t traj_stride, const float* freq, const float* sigmas,
+                      int64_t batch, void* stream);
+
 /* DPoser prior: perturb -> one_step_denoise -> weighted L2 -- run/completion.py:105-149,
  * run/smplify.py:69-107, run/motion_denoising.py:99-143.  All samples share time t.
  *   x0 [B, D]; z [B, D] injected noise or NULL; x0_hat [B, D] or NULL; grad [B, D] = d loss/d x0
