@@ -105,6 +105,26 @@ class RenderArgs(C.Structure):
                 ("face_id", C.c_void_p), ("mesh_id", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class RigidAlignArgs(C.Structure):
+    """dposer_rigid_align_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("batch", C.c_int64), ("num_points", C.c_int32), ("transform", C.c_void_p),
+                ("aligned", C.c_void_p), ("mean_dist", C.c_void_p)]
+
+
+class RegressJointsArgs(C.Structure):
+    """dposer_regress_joints_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("vertices", C.c_void_p), ("batch", C.c_int64), ("num_vertices", C.c_int32), ("row_ptr", C.c_void_p), ("col", C.c_void_p),
+                ("weight", C.c_void_p), ("num_rows", C.c_int32), ("joints", C.c_void_p)]
+
+
+class EhfEvalArgs(C.Structure):
+    """dposer_ehf_eval_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("pred_vertices", C.c_void_p), ("gt_vertices", C.c_void_p), ("batch", C.c_int64), ("num_vertices", C.c_int32),
+                ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("weight", C.c_void_p), ("num_rows", C.c_int32), ("gt_rotation", C.c_void_p),
+                ("pelvis_row", C.c_int32), ("pa_mpjpe", C.c_void_p), ("mpjpe", C.c_void_p), ("pred_joints", C.c_void_p),
+                ("gt_joints", C.c_void_p), ("aligned_joints", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -154,6 +174,10 @@ SIGNATURES = {
     "dposer_render_scratch_bytes": (i64, [i64, i32, i32, i64, i32, i32]),
     "dposer_render_meshes": (C.c_int, [C.POINTER(RenderArgs), vp]),
     "dposer_mesh_self_intersections": (C.c_int, [C.POINTER(MeshSiArgs), vp]),
+    "dposer_rigid_align": (C.c_int, [C.POINTER(RigidAlignArgs), vp]),
+    "dposer_regress_joints": (C.c_int, [C.POINTER(RegressJointsArgs), vp]),
+    "dposer_ehf_eval_scratch_bytes": (i64, [i64, i32]),
+    "dposer_ehf_eval": (C.c_int, [C.POINTER(EhfEvalArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),
     "dposer_dsm_loss_fwd_bwd_bucketed": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,

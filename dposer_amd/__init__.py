@@ -36,9 +36,11 @@ _ALIASES = {
     "lib.utils.misc": "dposer_amd.utils.misc",
     "lib.utils.generic": "dposer_amd.utils.generic",
     "lib.utils.metric": "dposer_amd.utils.metric",
+    "lib.utils.preprocess": "dposer_amd.utils.preprocess",
     "lib.dataset": "dposer_amd.dataset",
     "lib.dataset.AMASS": "dposer_amd.dataset.AMASS",
     "lib.dataset.EvaSampler": "dposer_amd.dataset.EvaSampler",
+    "lib.dataset.mocap_dataset": "dposer_amd.dataset.mocap_dataset",
     "configs": "dposer_amd.configs",
     "configs.default_amass_configs": "dposer_amd.configs.default_amass_configs",
     "configs.subvp": "dposer_amd.configs.subvp",

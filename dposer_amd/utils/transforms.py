@@ -6,9 +6,10 @@ All four directions are HIP kernels (dposer_rot6d_to_rotmat, dposer_rodrigues, d
 dposer_rot6d_to_axis_angle).  The reference delegates the axis-angle <-> matrix directions to the un-vendored
 ``torchgeometry``; its published algorithms are restated (torchgeometry is absent and the reference holds no test for them:
 parity unpinned against torchgeometry itself, but pinned against ``scipy.spatial.transform.Rotation`` -- an independent
-implementation of the same maps -- in tests/test_gpu_fk.py).  Camera / Procrustes helpers of
-the reference are host-side numpy outside the hot path and are not rebuilt.
+implementation of the same maps -- in tests/test_gpu_fk.py).  ``rigid_transform_3D`` / ``rigid_align`` (:264-286) run as one batched
+HIP call (dposer_rigid_align); ``procrustes`` / ``align_to_gt`` (:48-155) have no caller in the reference and are not rebuilt.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -82,3 +83,57 @@ def cam_crop2full(crop_cam, center, scale, full_img_shape, focal_length):
 def estimate_focal_length(img_h, img_w):
     """Focal length of a ~55 degree field of view: the image diagonal (transforms.py:193-194)."""
     return (img_w * img_w + img_h * img_h) ** 0.5
+
+
+def rigid_align_device(src, dst, transform=True, aligned=True, mean_dist=True):
+    """dposer_rigid_align on device tensors ``src``, ``dst`` [B, N, 3]: (transform [B, 13] = (c, R row-major, t), aligned [B, N, 3],
+    mean_dist [B]), None for the outputs not asked for.  One launch, no allocation inside the call, no host synchronisation."""
+    _C.require_gpu(src, "rigid_align src")
+    _C.require_gpu(dst, "rigid_align dst")
+    if src.dim() != 3 or src.shape[-1] != 3 or src.shape != dst.shape or src.shape[1] < 1:
+        raise ValueError(f"rigid_align: point sets must both be [B, N, 3] with N >= 1, got {tuple(src.shape)} and {tuple(dst.shape)}")
+    src, dst = src.contiguous().float(), dst.contiguous().float()
+    B, N = src.shape[0], src.shape[1]
+    T = torch.empty(B, 13, dtype=torch.float32, device=src.device) if transform else None
+    out = torch.empty_like(src) if aligned else None
+    md = torch.empty(B, dtype=torch.float32, device=src.device) if mean_dist else None
+    if B:
+        args = _C.RigidAlignArgs(src.data_ptr(), dst.data_ptr(), B, N, T.data_ptr() if transform else None,
+                                 out.data_ptr() if aligned else None, md.data_ptr() if mean_dist else None)
+        _C.check(_C.lib().dposer_rigid_align(args, _C.stream_ptr()), "dposer_rigid_align")
+    return T, out, md
+
+
+def _as_device_pairs(A, B):
+    """(A, B) as device tensors [B, N, 3] + how to hand results back: host arrays are moved to the GPU (there is no CPU arithmetic path)."""
+    is_np = not torch.is_tensor(A)
+    if is_np:
+        np_dtype = np.float64 if np.asarray(A).dtype == np.float64 else np.float32
+        A = torch.as_tensor(np.ascontiguousarray(A, dtype=np.float32), device="cuda")
+        B = torch.as_tensor(np.ascontiguousarray(np.asarray(B), dtype=np.float32), device="cuda")
+    else:
+        np_dtype = None
+        B = torch.as_tensor(B, device=A.device)
+    single = A.dim() == 2
+    if single:
+        A, B = A[None], B[None]
+    back = (lambda x: x.cpu().numpy().astype(np_dtype)) if is_np else (lambda x: x)
+    return A, B, single, back
+
+
+def rigid_transform_3D(A, B):
+    """transforms.py:264-280: the similarity (c, R, t) taking the points A onto B, for one pair [N, 3] or a batch [B, N, 3] (then c [B],
+    R [B, 3, 3], t [B, 3]).  numpy in -> numpy out; device tensor in -> device tensors out, without a synchronisation."""
+    A, B, single, back = _as_device_pairs(A, B)
+    T, _, _ = rigid_align_device(A, B, aligned=False, mean_dist=False)
+    c, R, t = T[:, 0], T[:, 1:10].reshape(-1, 3, 3), T[:, 10:13]
+    if single:
+        c, R, t = c[0], R[0], t[0]
+    return back(c), back(R), back(t)
+
+
+def rigid_align(A, B):
+    """transforms.py:283-286: A under the similarity that takes it onto B, [N, 3] or [B, N, 3]; numpy or device tensors as above."""
+    A, B, single, back = _as_device_pairs(A, B)
+    _, out, _ = rigid_align_device(A, B, transform=False, mean_dist=False)
+    return back(out[0] if single else out)

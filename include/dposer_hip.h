@@ -799,6 +799,77 @@ int64_t dposer_render_scratch_bytes(int64_t num_meshes, int32_t num_vertices, in
                                     int32_t width);
 int dposer_render_meshes(const dposer_render_args* args, void* stream);
 
+/* Rigid (similarity) alignment -- lib/utils/transforms.py:264-286 (rigid_transform_3D, rigid_align) for B independent pairs of point sets
+ * src = A, dst = B, each [batch, num_points, 3] fp32, num_points >= 1.  Per pair:
+ *   centroids a, b;  H = (A - a)^T (B - b) / N;  H = U S V^T;  R = V U^T;  if det R < 0 the last singular value and the last row of V^T
+ *   are negated and R re-formed, so R is always a proper rotation;  c = sum(s) / sum over axes of the population variance of A
+ *   (np.var, ddof 0);  t = b - c R a.
+ * Outputs, each optional (NULL = not written): transform [batch, 13] = (c, R row-major, t); aligned [batch, num_points, 3] = c R a + t;
+ *   mean_dist [batch] = mean over points of ||aligned - dst||_2, in the caller's unit.
+ * Arithmetic: centroids, H, the variance, the 3 x 3 decomposition (one-sided Jacobi, written in the kernel), c, R and t in fp64, from
+ *   moments taken relative to the pair's first point; the transform is rounded once to fp32, and c R a + t and the distances are fp32
+ *   FMAs on the rounded transform (distances summed in fp64).  Every sum runs in a fixed order that depends on num_points alone (no
+ *   atomics): the bits of a pair do not depend on batch, on its position, or on how a batch is split into calls.
+ * A pair whose source has zero variance (num_points = 1 included) or that holds a non-finite coordinate gets NaN in all its outputs, as
+ *   the reference's division by zero does; other pairs are unaffected.  Collinear sources are ill-conditioned here as in the reference.
+ * Allocates nothing, never synchronises the host. */
+typedef struct dposer_rigid_align_args {
+    const float* src;         /* [batch, num_points, 3] */
+    const float* dst;         /* [batch, num_points, 3] */
+    int64_t batch;
+    int32_t num_points;
+    float* transform;         /* [batch, 13] or NULL */
+    float* aligned;           /* [batch, num_points, 3] or NULL */
+    float* mean_dist;         /* [batch] or NULL */
+} dposer_rigid_align_args;
+int dposer_rigid_align(const dposer_rigid_align_args* args, void* stream);
+
+/* Joint regression -- np.dot(J_regressor, mesh)[:R] of lib/dataset/mocap_dataset.py:72-73 for B meshes: joints [batch, num_rows, 3] =
+ * W vertices [batch, num_vertices, 3] with W in CSR form (row_ptr [num_rows + 1], col, weight; the host builds it once per model).  A
+ * row's entries are summed in CSR order in fp64 and rounded once to fp32; only the vertices a row names are read.  The weights are
+ * fp32: a regressor stored in fp64 is rounded once per weight before the sums (up to 6e-8 relative on a joint, 2e-7 m at 4 m; the
+ * regressors of the SMPL-family files the loader reads are kept in fp32 by the body model as well).  col is device data and not
+ * range-checked here.  Allocates nothing, never synchronises the host. */
+typedef struct dposer_regress_joints_args {
+    const float* vertices;
+    int64_t batch;
+    int32_t num_vertices;
+    const int32_t* row_ptr;
+    const int32_t* col;
+    const float* weight;
+    int32_t num_rows;
+    float* joints;
+} dposer_regress_joints_args;
+int dposer_regress_joints(const dposer_regress_joints_args* args, void* stream);
+
+/* EHF evaluation -- MocapDataset.eval_EHF (lib/dataset/mocap_dataset.py:61-84) for B images in one call.  Both meshes are regressed to
+ * num_rows joints (the rule of dposer_regress_joints); the ground-truth joints are rotated by gt_rotation (row-major 3 x 3, applied to the
+ * fp64 sums before rounding; NULL = identity; the reference rotates the whole mesh first, which is the same up to rounding because the
+ * regressor is linear); the predicted joints are aligned onto them (the rule of dposer_rigid_align);
+ *   pa_mpjpe = 1000 mean_j ||aligned_j - gt_j||;   mpjpe = 1000 mean_j ||pred_j - pred_pelvis + gt_pelvis - gt_j||  (pelvis = pelvis_row).
+ * pred_joints, gt_joints, aligned_joints [batch, num_rows, 3] are optional outputs.  scratch: dposer_ehf_eval_scratch_bytes(batch,
+ * num_rows) bytes, 256-byte aligned.  Queues its kernels on the stream; allocates nothing, never synchronises the host. */
+typedef struct dposer_ehf_eval_args {
+    const float* pred_vertices;   /* [batch, num_vertices, 3] */
+    const float* gt_vertices;     /* [batch, num_vertices, 3] */
+    int64_t batch;
+    int32_t num_vertices;
+    const int32_t* row_ptr;
+    const int32_t* col;
+    const float* weight;
+    int32_t num_rows;
+    const float* gt_rotation;     /* [3, 3] or NULL */
+    int32_t pelvis_row;
+    float* pa_mpjpe;              /* [batch], millimetres when the meshes are in metres */
+    float* mpjpe;                 /* [batch] */
+    float* pred_joints;
+    float* gt_joints;
+    float* aligned_joints;
+    void* scratch;
+} dposer_ehf_eval_args;
+int64_t dposer_ehf_eval_scratch_bytes(int64_t batch, int32_t num_rows);
+int dposer_ehf_eval(const dposer_ehf_eval_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
