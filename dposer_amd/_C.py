@@ -125,6 +125,34 @@ class EhfEvalArgs(C.Structure):
                 ("gt_joints", C.c_void_p), ("aligned_joints", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class DrawSkeletonsArgs(C.Structure):
+    """dposer_draw_skeletons_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("joints", C.c_void_p), ("batch", C.c_int64), ("num_joints", C.c_int32), ("num_bones", C.c_int32), ("visible", C.c_void_p),
+                ("bones", C.c_void_p), ("bone_color", C.c_void_p), ("joint_color", C.c_void_p), ("s", C.c_float), ("X0", C.c_float),
+                ("Y0", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("y_up", C.c_int32), ("z_toward_viewer", C.c_int32),
+                ("line_width", C.c_float), ("joint_radius", C.c_float), ("height", C.c_int32), ("width", C.c_int32),
+                ("background", C.c_void_p), ("background_stride", C.c_int64), ("background_color", C.c_uint8 * 4), ("rgb", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
+MAX_PANELS = 8                       # DPOSER_MAX_PANELS
+DRAW_MAX_PRIMITIVES = 4096           # DPOSER_DRAW_MAX_PRIMITIVES
+
+
+class Panel(C.Structure):
+    """dposer_panel (include/dposer_hip.h), field for field."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("crop_x", C.c_int32),
+                ("crop_y", C.c_int32), ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("resize_h", C.c_int32), ("resize_w", C.c_int32),
+                ("cell_h", C.c_int32), ("cell_w", C.c_int32), ("fill", C.c_uint8 * 4), ("strip", C.c_void_p), ("strip_h", C.c_int32),
+                ("x_offset", C.c_int32)]
+
+
+class ComposeArgs(C.Structure):
+    """dposer_compose_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("panels", C.POINTER(Panel)), ("num_panels", C.c_int32), ("num_frames", C.c_int64), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("out_fill", C.c_uint8 * 4), ("out", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -178,6 +206,9 @@ SIGNATURES = {
     "dposer_regress_joints": (C.c_int, [C.POINTER(RegressJointsArgs), vp]),
     "dposer_ehf_eval_scratch_bytes": (i64, [i64, i32]),
     "dposer_ehf_eval": (C.c_int, [C.POINTER(EhfEvalArgs), vp]),
+    "dposer_draw_skeletons_scratch_bytes": (i64, [i64, i32, i32]),
+    "dposer_draw_skeletons": (C.c_int, [C.POINTER(DrawSkeletonsArgs), vp]),
+    "dposer_compose_panels": (C.c_int, [C.POINTER(ComposeArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),
     "dposer_dsm_loss_fwd_bwd_bucketed": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,

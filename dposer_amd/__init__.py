@@ -37,6 +37,7 @@ _ALIASES = {
     "lib.utils.generic": "dposer_amd.utils.generic",
     "lib.utils.metric": "dposer_amd.utils.metric",
     "lib.utils.preprocess": "dposer_amd.utils.preprocess",
+    "lib.utils.motion_video": "dposer_amd.utils.motion_video",
     "lib.dataset": "dposer_amd.dataset",
     "lib.dataset.AMASS": "dposer_amd.dataset.AMASS",
     "lib.dataset.EvaSampler": "dposer_amd.dataset.EvaSampler",

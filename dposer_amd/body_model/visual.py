@@ -7,7 +7,25 @@ Shading is Lambert plus ambient, ``c = clamp(base * (ambient + sum_l I_l max(0, 
 physically based shader divides its Lambert term by pi and adds a specular lobe; the presets below take pyrender's light intensities
 divided by pi (and pytorch3d's Phong weights for ``faster_render``), so the images read like the reference's.  Parity with pyrender or
 pytorch3d is not pinned.  Images are written as true RGB (the reference's ``render_mesh`` route hands RGB arrays to ``cv2.imwrite``,
-which expects BGR, so its saved bodies are channel-swapped).  Skeleton plots and videos are not here."""
+which expects BGR, so its saved bodies are channel-swapped).
+
+Skeleton plots (``vis_skeletons``, ``visualize_skeleton_sequence``, ``visualize_3d_skeleton``; visual.py:18-119, one matplotlib 3-D figure
+per frame there) go through ``draw_skeletons``: every frame of a sequence in one ``dposer_draw_skeletons`` call (csrc/draw.hip).  The rules,
+in full in include/dposer_hip.h:
+
+* view: orthographic, an upright front view of the joints handed to ``vis_skeletons`` (its flip by pi about x followed by matplotlib's
+  ``plot(x, z, -y)`` at ``view_init(0, -90)``): x to the right, y up, a larger z nearer;
+* frames are 640 x 480 on white, as ``plt.savefig`` makes them; a sequence shares one scale and one centre (min / max over all frames,
+  padding ratio 1.2, the largest padded extent of the three axes spans min(H, W), the x / y centre of the bounds lands on the image
+  centre); a single frame uses its own bounds; ``ax_lims`` (x, y, z bounds already padded) is honoured the same way;
+* bones are segments ``LINE_WIDTH_PX`` wide (matplotlib's linewidth 2 pt at 100 dpi), joints discs of radius ``JOINT_RADIUS_PX`` (its
+  default 6 pt marker); coverage is ``clamp(r + 0.5 - distance, 0, 1)`` at pixel centres;
+* painter's order per frame, one depth per primitive (a bone: the mean of its ends; a disc: its joint, 1e-3 nearer), far to near;
+* colours are what the reference plots: matplotlib's ``rainbow`` at ``linspace(0, 1, K + 2)`` with red and blue swapped (visual.py:35),
+  frozen in ``SKELETON_COLORS_21`` for the SMPL bone list; a joint's disc takes the colour of the last bone that touches it.
+
+Pixel parity with matplotlib is not a goal and is not claimed (no axes box perspective, no figure margins, no title text: ``title`` is
+accepted and ignored).  A ``.mp4`` path produces an uncompressed ``.avi`` beside it (``utils.motion_video.write_video``)."""
 import colorsys
 import ctypes as C
 import math
@@ -420,3 +438,184 @@ def write_image(path, rgb_uint8):
     except ImportError:
         raise RuntimeError(f"writing {path!r} needs PIL (only .png is written without it)") from None
     Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).save(path)
+
+
+# ---- skeleton plots (visual.py:18-119) -----------------------------------------------------------------------------------------------
+SKELETON_SIZE = (480, 640)            # (H, W) of plt.savefig's default 6.4 x 4.8 in figure at 100 dpi
+SKELETON_PADDING = 1.2                # visualize_skeleton_sequence's padding_ratio
+LINE_WIDTH_PX = 2.0 * 100.0 / 72.0    # linewidth=2 (points) at 100 dpi
+JOINT_RADIUS_PX = 3.0 * 100.0 / 72.0  # scatter's default marker: 6 pt across
+SKELETON_FPS = 20.0
+
+# matplotlib's 'rainbow' (256-entry table) at linspace(0, 1, 23)[:21], red and blue swapped as visual.py:35 swaps them; uint8 RGB
+SKELETON_COLORS_21 = (
+    (255, 0, 128), (254, 34, 106), (252, 71, 82), (249, 104, 60), (245, 137, 36), (239, 167, 12), (232, 192, 10), (224, 214, 34),
+    (214, 232, 58), (204, 244, 80), (193, 252, 104), (180, 255, 128), (167, 252, 150), (152, 244, 174), (138, 232, 196),
+    (122, 214, 220), (105, 192, 244), (89, 167, 255), (71, 137, 255), (53, 104, 255), (36, 71, 255))
+
+
+def rainbow_swapped(n):
+    """uint8 [n, 3]: matplotlib's ``rainbow`` colormap at ``linspace(0, 1, n + 2)[:n]`` with red and blue swapped -- the colours of
+    visual.py:33-35 for n bones.  The colormap's three channel functions (|2x - 0.5|, sin(pi x), cos(pi x / 2), clipped to [0, 1]) sampled
+    through its 256-entry table, as ``cmap(x)`` looks them up."""
+    if n == len(SKELETON_COLORS_21):
+        return np.asarray(SKELETON_COLORS_21, dtype=np.uint8)
+    grid = np.linspace(0.0, 1.0, 256)
+    lut = np.clip(np.stack([np.abs(2 * grid - 0.5), np.sin(np.pi * grid), np.cos(np.pi * grid / 2)], 1), 0.0, 1.0)
+    x = np.linspace(0.0, 1.0, n + 2)[:n]
+    idx = np.minimum((x * 256).astype(np.int64), 255)
+    rgb = lut[idx]
+    return np.rint(rgb[:, ::-1] * 255).astype(np.uint8)
+
+
+def skeleton_joint_colors(bones, bone_color, num_joints):
+    """uint8 [J, 3]: every joint in the colour of the last bone that touches it (the reference scatters both ends of bone l in colour l,
+    later bones over earlier ones); joints no bone touches are black."""
+    out = np.zeros((num_joints, 3), np.uint8)
+    for (a, b), c in zip(np.asarray(bones).reshape(-1, 2), np.asarray(bone_color)):
+        out[a] = c
+        out[b] = c
+    return out
+
+
+def skeleton_view(lo, hi, image_size=SKELETON_SIZE, padding=SKELETON_PADDING, padded=False):
+    """(s, X0, Y0, cx, cy) of the view that fits the bounds ``lo`` / ``hi`` [3]: the largest (padded) extent of the three axes spans
+    min(H, W), the x / y centre of the bounds maps to the image centre.  ``padded``: the bounds already include the padding."""
+    H, W = image_size
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    ext = float(np.max(hi - lo)) * (1.0 if padded else padding)
+    s = min(H, W) / ext if ext > 0 and np.isfinite(ext) else 1.0
+    return (s, float((lo[0] + hi[0]) / 2), float((lo[1] + hi[1]) / 2), W / 2.0, H / 2.0)
+
+
+def draw_skeletons(joints, bones, image_size=SKELETON_SIZE, view=None, bone_color=None, joint_color=None, visible=None,
+                   line_width=LINE_WIDTH_PX, joint_radius=JOINT_RADIUS_PX, background=None, background_color=(255, 255, 255), y_up=True,
+                   z_toward_viewer=True):
+    """Draw ``joints [B, J, 3]`` (device tensor) as ``bones [K, 2]`` and J discs: uint8 ``[B, H, W, 3]`` on the device, one
+    ``dposer_draw_skeletons`` call (rules: the module docstring and include/dposer_hip.h).
+
+    ``view`` = (s, X0, Y0, cx, cy): screen x = cx + s (X - X0), screen y = cy -/+ s (Y - Y0) (``y_up``); None fits the finite joints of
+    the whole batch (``skeleton_view``).  ``bone_color`` uint8 [K, 3] (None: ``rainbow_swapped(K)``), ``joint_color`` uint8 [J, 3] (None:
+    the last bone touching each joint), ``visible`` [J] (None: all).  ``background`` uint8 [H, W, 3] or [B, H, W, 3], else
+    ``background_color``.  ROCm tensors only; no CPU fallback."""
+    from .. import _C
+    if not torch.is_tensor(joints):
+        raise ValueError("joints must be a torch tensor on the GPU")
+    _C.require_gpu(joints, "joints")
+    dev = joints.device
+    if joints.dim() != 3 or joints.shape[-1] != 3:
+        raise ValueError(f"joints must be [B, J, 3], got {tuple(joints.shape)}")
+    B, J = int(joints.shape[0]), int(joints.shape[1])
+    H, W = (int(v) for v in image_size)
+    if H < 1 or W < 1:
+        raise ValueError(f"image_size must be >= 1 in both axes, got {(H, W)}")
+    bones_np = np.asarray(bones.cpu() if torch.is_tensor(bones) else bones, dtype=np.int64).reshape(-1, 2)
+    K = int(bones_np.shape[0])
+    if K + J > _C.DRAW_MAX_PRIMITIVES:
+        raise ValueError(f"{K} bones + {J} joints: more than {_C.DRAW_MAX_PRIMITIVES} primitives per frame are not supported")
+    if K and (bones_np.min() < 0 or bones_np.max() >= J):
+        raise ValueError(f"bone ends must lie in [0, {J})")
+    bcol = rainbow_swapped(K) if bone_color is None else np.asarray(bone_color)
+    if bcol.dtype != np.uint8 or bcol.shape != (K, 3):
+        raise ValueError(f"bone_color must be uint8 [{K}, 3], got {bcol.dtype} {bcol.shape}")
+    jcol = skeleton_joint_colors(bones_np, bcol, J) if joint_color is None else np.asarray(joint_color)
+    if jcol.dtype != np.uint8 or jcol.shape != (J, 3):
+        raise ValueError(f"joint_color must be uint8 [{J}, 3], got {jcol.dtype} {jcol.shape}")
+    j = joints.detach().to(torch.float32).contiguous()
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return out
+    if view is None:
+        ok = torch.isfinite(j).all(dim=2)
+        if visible is not None:
+            ok = ok & torch.as_tensor(np.asarray(visible).reshape(-1) > 0, device=dev)[None, :]
+        pts = j[ok]
+        if pts.numel():
+            view = skeleton_view(pts.min(dim=0).values.cpu().numpy(), pts.max(dim=0).values.cpu().numpy(), (H, W))
+        else:
+            view = (1.0, 0.0, 0.0, W / 2.0, H / 2.0)
+    s, X0, Y0, cx, cy = (float(v) for v in view)
+    vis_t = None if visible is None else torch.as_tensor((np.asarray(visible).reshape(-1) > 0).astype(np.uint8), device=dev)
+    if vis_t is not None and vis_t.shape != (J,):
+        raise ValueError(f"visible must be [{J}], got {tuple(vis_t.shape)}")
+    bg, bg_stride = None, 0
+    if background is not None:
+        bg = torch.as_tensor(background, device=dev) if not torch.is_tensor(background) else background.to(dev)
+        if bg.dtype != torch.uint8 or tuple(bg.shape[-3:]) != (H, W, 3) or bg.dim() not in (3, 4) or (bg.dim() == 4 and bg.shape[0] != B):
+            raise ValueError(f"background must be uint8 [H, W, 3] or [B, H, W, 3], got {bg.dtype} {tuple(bg.shape)}")
+        bg = bg.contiguous()
+        bg_stride = H * W * 3 if bg.dim() == 4 else 0
+    bgc = [int(c) for c in np.broadcast_to(np.asarray(background_color), (3,))] + [0]
+    bones_t = torch.as_tensor(bones_np.astype(np.int32), device=dev).contiguous()
+    bcol_t = torch.as_tensor(np.ascontiguousarray(bcol), device=dev)
+    jcol_t = torch.as_tensor(np.ascontiguousarray(jcol), device=dev)
+    l = _C.lib()
+    tiles = -(-H // 16) * -(-W // 64)
+    per_call = max(1, (2 ** 31 - 1) // tiles)
+    for b0 in range(0, B, per_call):
+        nb = min(B, b0 + per_call) - b0
+        scratch = torch.empty((int(l.dposer_draw_skeletons_scratch_bytes(nb, J, K)),), dtype=torch.uint8, device=dev)
+        a = _C.DrawSkeletonsArgs(joints=j[b0].data_ptr() if J else None, batch=nb, num_joints=J, num_bones=K,
+                                 visible=None if vis_t is None else vis_t.data_ptr(), bones=bones_t.data_ptr() if K else None,
+                                 bone_color=bcol_t.data_ptr() if K else None, joint_color=jcol_t.data_ptr() if J else None, s=s, X0=X0, Y0=Y0,
+                                 cx=cx, cy=cy, y_up=1 if y_up else 0, z_toward_viewer=1 if z_toward_viewer else 0,
+                                 line_width=float(line_width), joint_radius=float(joint_radius), height=H, width=W,
+                                 background=None if bg is None else (bg[b0] if bg.dim() == 4 else bg).data_ptr(), background_stride=bg_stride,
+                                 background_color=(C.c_uint8 * 4)(*bgc), rgb=out[b0].data_ptr(), scratch=scratch.data_ptr())
+        _C.check(l.dposer_draw_skeletons(C.byref(a), _C.stream_ptr()), "dposer_draw_skeletons")
+    return out
+
+
+def _plot_frames(joints_np, kpt_3d_vis, kps_lines, ax_lims):
+    """The frames of visualize_3d_skeleton for ``joints_np [B, J, 3]`` in its frame (the points vis_skeletons has flipped about x: the
+    figure shows x to the right, -y up, and a larger z farther): uint8 [B, 480, 640, 3] on the device."""
+    dev = _dev()
+    j = torch.as_tensor(np.asarray(joints_np, dtype=np.float32), device=dev)
+    vis = None if kpt_3d_vis is None else np.asarray(kpt_3d_vis).reshape(len(kpt_3d_vis), -1)[:, 0] > 0
+    view = None if ax_lims is None else skeleton_view([ax_lims[0], ax_lims[2], ax_lims[4]], [ax_lims[1], ax_lims[3], ax_lims[5]], padded=True)
+    return draw_skeletons(j, np.asarray(kps_lines), view=view, visible=vis, y_up=False, z_toward_viewer=False)
+
+
+def visualize_3d_skeleton(kpt_3d, kpt_3d_vis, kps_lines, title=None, output_path=None, ax_lims=None):
+    """visual.py:18-64: one skeleton frame ``kpt_3d [J, 3]``; written to ``output_path`` when given (the reference opens a window
+    otherwise) and returned as uint8 [480, 640, 3].  ``title`` is accepted and ignored."""
+    img = _plot_frames(np.asarray(kpt_3d)[None], kpt_3d_vis, kps_lines, ax_lims)[0].cpu().numpy()
+    if output_path:
+        write_image(output_path, img)
+    return img
+
+
+def visualize_skeleton_sequence(joints_seq, kpt_3d_vis, kps_lines, output_path):
+    """visual.py:67-104: every frame of ``joints_seq [T, J, 3]`` under one view, drawn in one call.  A path ending in ``.mp4`` gets a
+    20 fps video (written as ``.avi``, see ``utils.motion_video.write_video``; the real path is returned), a path without extension is
+    a directory of ``frame_%04d.png``; anything else raises the reference's ValueError."""
+    joints_seq = np.asarray(joints_seq)
+    is_video = output_path.endswith(".mp4")
+    if not is_video and os.path.splitext(output_path)[1]:
+        raise ValueError("The output_path must end with .mp4 or no extension!")
+    pts = joints_seq.reshape(-1, 3)
+    joint_min, joint_max = np.min(pts, axis=0), np.max(pts, axis=0)
+    center, half = (joint_max + joint_min) / 2, SKELETON_PADDING * (joint_max - joint_min) / 2
+    ax_lims = [center[0] - half[0], center[0] + half[0], center[1] - half[1], center[1] + half[1], center[2] - half[2], center[2] + half[2]]
+    frames = _plot_frames(joints_seq, kpt_3d_vis, kps_lines, ax_lims)
+    if is_video:
+        from ..utils.motion_video import write_video
+        return write_video(output_path, frames, SKELETON_FPS)
+    os.makedirs(output_path, exist_ok=True)
+    rgb = frames.cpu().numpy()
+    for i in range(len(rgb)):
+        write_image(os.path.join(output_path, f"frame_{i:04d}.png"), rgb[i])
+    return output_path
+
+
+def vis_skeletons(joints_3d, output_path):
+    """visual.py:107-119: 22 SMPL joints, one frame ``[22, 3]`` or a sequence ``[T, 22, 3]``, as an upright front view."""
+    from ..utils.transforms import get_rotation_matrix_x, rotate_points
+    from .utils import get_smpl_skeleton
+    joints_3d = rotate_points(np.asarray(joints_3d), get_rotation_matrix_x(np.pi))
+    kpt_3d_vis = np.ones((22, 1))
+    kps_lines = get_smpl_skeleton()
+    if len(joints_3d.shape) == 2:
+        visualize_3d_skeleton(joints_3d, kpt_3d_vis, kps_lines, output_path=output_path)
+    elif len(joints_3d.shape) == 3:
+        visualize_skeleton_sequence(joints_3d, kpt_3d_vis, kps_lines, output_path)

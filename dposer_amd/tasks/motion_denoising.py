@@ -8,9 +8,14 @@ The frames of one sequence are coupled by the temporal term, so data parallelism
 The whole loop is ONE call, ``dposer_motion_denoise_optimize`` (axis-angle or 6-D rotation representation, sub-VP / VP SDE, positional or Fourier time embedding):
 all steps are queued from C, the loss gradients and torch.optim.Adam's update are kernels, nothing returns to the host in
 between.  Other configurations (and ``fused=False``) run the same step through autograd and torch's Adam.
+
+``optimize(..., vis=True)`` writes what the reference writes into ``out_path`` (motion_denoising.py:204-207,287-290): the skeleton frames
+of the noisy joints, the ground-truth and result body renders, the three-panel merged frames and the motion video -- each through one
+batched call (``vis_skeletons``, ``MotionDenoise.visualize``, ``seq_to_video``).
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -45,6 +50,12 @@ def _normalize_with_grad(nz, pose):
         return nz.offline_normalize(pose, from_axis=True)
     six = _axis_angle_to_rot6d_autograd(pose.reshape(-1, 3)).reshape(*pose.shape[:-1], -1)
     return nz.offline_normalize(six, from_axis=False)
+
+
+# the canvas and camera of run/motion_denoising.py:30-32 (``visualize`` renders over a white 512 x 384 canvas)
+VIS_CANVAS = (512, 384)
+VIS_FOCAL = (1500, 1500)
+VIS_PRINCPT = (200, 192)
 
 
 class MotionDenoise:
@@ -233,13 +244,49 @@ class MotionDenoise:
         r = lambda x: x.reshape(S, F).cpu().numpy()
         return {"init_MPJPE": r(init_mpjpe), "MPJPE": r(mpjpe), "MPVPE": r(mpvpe), "pose_body": final}
 
+    @staticmethod
+    def visualize(vertices, faces, out_path, render=False, prefix="out", save_mesh=False, faster=False, device=None):
+        """motion_denoising.py:175-197: meshes as ``meshes/{prefix}_%04d.obj`` and / or renders as ``renders/{prefix}_%04d.png`` (front
+        view over the white 512 x 384 canvas, every frame in one render call) or, with ``faster``, ``renders/{prefix}_%04d.jpg`` through
+        ``faster_render``."""
+        from ..body_model import visual
+        os.makedirs(out_path, exist_ok=True)
+        if save_mesh:
+            v, f = vertices.detach().cpu().numpy(), np.asarray(faces.cpu() if torch.is_tensor(faces) else faces)
+            os.makedirs(os.path.join(out_path, "meshes"), exist_ok=True)
+            for i in range(len(v)):
+                visual.save_obj(v[i], f, os.path.join(out_path, "meshes", "{}_{:04}.obj".format(prefix, i)))
+        if render:
+            target = os.path.join(out_path, "renders")
+            os.makedirs(target, exist_ok=True)
+            if faster:
+                assert device is not None
+                visual.faster_render(vertices, faces, target, prefix + "_{:04}.jpg", device)
+            else:
+                H, W = VIS_CANVAS
+                dev = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else visual._dev()
+                rgb, mask = visual._render_mesh_batch(vertices, faces, H, W, VIS_FOCAL, VIS_PRINCPT, ["front"] * len(vertices), dev)
+                white = torch.full_like(rgb, 255)
+                rgb = torch.where(mask[..., None], rgb, white).cpu().numpy()
+                for i in range(len(rgb)):
+                    visual.write_image(os.path.join(target, "{}_{:04}.png".format(prefix, i)), rgb[i])
+
     def optimize(self, joints3d, gt_poses=None, time_strategy="1", sample_trun=2.0, sample_time=990, iterations=5, steps_per_iter=50,
                  verbose=False, vis=False, noise=None, init_poses=None, fused=None):
-        """motion_denoising.py:199-300 (visualisation dropped).  Returns {'init_MPJPE', 'MPJPE', 'MPVPE'} in cm per frame.
-        ``fused``: None = the one-call loop when the configuration supports it, False = step by step through autograd."""
+        """motion_denoising.py:199-300.  Returns {'init_MPJPE', 'MPJPE', 'MPVPE'} in cm per frame.
+        ``fused``: None = the one-call loop when the configuration supports it, False = step by step through autograd.
+        ``vis``: also write the skeleton frames, ``gt_*`` / ``out_*`` renders, ``merges/`` and the motion video into ``self.out_path``
+        (the video as ``motion.avi``, see utils.motion_video.write_video); the returned metrics do not depend on it."""
         bm = self.body_model
+        if vis and self.out_path is None:
+            raise ValueError("optimize(vis=True) needs the module's out_path")
         with torch.no_grad():
             gt = bm(betas=self.betas, pose_body=gt_poses)
+            if vis:
+                from ..body_model.visual import vis_skeletons
+                vis_skeletons(joints3d.detach().cpu().numpy(), os.path.join(self.out_path, "renders"))
+                print("skeleton figures saved")
+                self.visualize(gt.v, gt.f, self.out_path, render=True, prefix="gt", device=self.device)
             joint_error = joints3d - gt.Jtr[:, :22]
             init_mpjpe = torch.mean(torch.sqrt(torch.sum(joint_error * joint_error, dim=2)), dim=1) * 100.0
         init_joints = joints3d.detach()
@@ -283,6 +330,11 @@ class MotionDenoise:
             smooth = gaussian_smoothing(final, window_size=3, sigma=2)
             smooth[[0, -1]] = final[[0, -1]]
             out = bm(betas=self.betas, pose_body=smooth)
+            if vis:
+                from ..utils.motion_video import seq_to_video
+                self.visualize(out.v, out.f, self.out_path, render=True, prefix="out", device=self.device)
+                seq_to_video(os.path.join(self.out_path, "renders"), os.path.join(self.out_path, "merges"),
+                             video_path=os.path.join(self.out_path, "motion.mp4"))
             je = out.Jtr[:, :22] - gt.Jtr[:, :22]
             ve = out.v - gt.v
             mpjpe = torch.mean(torch.sqrt(torch.sum(je * je, dim=2)), dim=1) * 100.0

@@ -7,7 +7,8 @@ dposer_rot6d_to_axis_angle).  The reference delegates the axis-angle <-> matrix 
 ``torchgeometry``; its published algorithms are restated (torchgeometry is absent and the reference holds no test for them:
 parity unpinned against torchgeometry itself, but pinned against ``scipy.spatial.transform.Rotation`` -- an independent
 implementation of the same maps -- in tests/test_gpu_fk.py).  ``rigid_transform_3D`` / ``rigid_align`` (:264-286) run as one batched
-HIP call (dposer_rigid_align); ``procrustes`` / ``align_to_gt`` (:48-155) have no caller in the reference and are not rebuilt.
+HIP call (dposer_rigid_align); ``rotate_points`` / ``get_rotation_matrix_x`` / ``get_rotation_matrix_y`` (:289-312) are the host helpers
+of ``vis_skeletons``; ``procrustes`` / ``align_to_gt`` (:48-155) have no caller in the reference and are not rebuilt.
 """
 import numpy as np
 import torch
@@ -137,3 +138,18 @@ def rigid_align(A, B):
     A, B, single, back = _as_device_pairs(A, B)
     _, out, _ = rigid_align_device(A, B, transform=False, mean_dist=False)
     return back(out[0] if single else out)
+
+
+def rotate_points(points, rotation_matrix):
+    """transforms.py:289-290: ``points [..., 3]`` under ``rotation_matrix`` (host helper of ``vis_skeletons``)."""
+    return np.dot(points, rotation_matrix.T)
+
+
+def get_rotation_matrix_x(angle):
+    """transforms.py:293-301: rotation about the x axis."""
+    return np.array([[1, 0, 0], [0, np.cos(angle), -np.sin(angle)], [0, np.sin(angle), np.cos(angle)]])
+
+
+def get_rotation_matrix_y(angle):
+    """transforms.py:304-312: rotation about the y axis."""
+    return np.array([[np.cos(angle), 0, np.sin(angle)], [0, 1, 0], [-np.sin(angle), 0, np.cos(angle)]])

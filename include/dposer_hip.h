@@ -870,6 +870,88 @@ typedef struct dposer_ehf_eval_args {
 int64_t dposer_ehf_eval_scratch_bytes(int64_t batch, int32_t num_rows);
 int dposer_ehf_eval(const dposer_ehf_eval_args* args, void* stream);
 
+/* Skeleton plots -- what lib/body_model/visual.py:18-119 does with one matplotlib 3-D figure per frame (visualize_3d_skeleton,
+ * visualize_skeleton_sequence, vis_skeletons): B frames of J joints drawn as K bones and J discs in one call, every frame under the same
+ * orthographic view.  Pixel (row y, col x) is sampled at its centre (x + 0.5, y + 0.5).  All arithmetic fp32, no contraction.
+ * Projection: screen x = cx + s (X - X0);  screen y = cy - s (Y - Y0) when y_up = 1, cy + s (Y - Y0) when y_up = 0;  depth = -Z when
+ *   z_toward_viewer = 1 (larger Z is nearer), else Z.  A larger depth is farther.  y_up = 1, z_toward_viewer = 1 is the reference's view
+ *   (vis_skeletons flips the points by pi about x, then plots (x, z, -y) at view_init(0, -90): an upright front view of the input joints).
+ * Primitives: K bones, the screen-space segments between joints bones[k][0] and bones[k][1]; a bone is dropped when either end is
+ *   invisible (visible[j] == 0; visible NULL = all visible) or has a non-finite coordinate.  Then J discs at the joints, dropped on the
+ *   same conditions.  Primitive index: bone k -> k, disc j -> K + j.
+ * Coverage at a pixel centre: a = clamp(r + 0.5 - d, 0, 1); bone: d = distance to the segment (the nearest point a + t (b - a), t =
+ *   clamp((p - a) . (b - a) / |b - a|^2, 0, 1), t = 0 for a zero-length segment), r = line_width / 2; disc: d = distance to the centre,
+ *   r = joint_radius.
+ * Order: painter's, per frame.  One key per primitive: a bone's is 0.5 (depth_a + depth_b), a disc's its joint's depth - 1e-3 (a disc
+ *   lies in front of the bones that meet at it).  Painted far to near (descending key), ties in primitive index order (mplot3d orders
+ *   its artists the same way, one depth per artist).
+ * Colour: c starts as the background pixel (background [H, W, 3] + b * background_stride bytes for frame b, stride 0: shared; or
+ *   background_color when background is NULL); for each primitive in order with a > 0, c <- c (1 - a) + colour a per channel; the stored
+ *   byte is rint(c).
+ * Limits: num_bones + num_joints <= DPOSER_DRAW_MAX_PRIMITIVES; batch x tiles must fit 31 bits.  bones is device data and not
+ *   range-checked here.  scratch: dposer_draw_skeletons_scratch_bytes(batch, num_joints, num_bones) bytes, 256-byte aligned.  Addresses
+ *   are 64-bit throughout (batch x H x W x 3 may pass 2^31).  No atomics; allocates nothing, never synchronises the host. */
+#define DPOSER_DRAW_MAX_PRIMITIVES 4096
+typedef struct dposer_draw_skeletons_args {
+    const float* joints;          /* [batch, num_joints, 3] */
+    int64_t batch;
+    int32_t num_joints;
+    int32_t num_bones;
+    const uint8_t* visible;       /* [num_joints] or NULL */
+    const int32_t* bones;         /* [num_bones, 2] */
+    const uint8_t* bone_color;    /* [num_bones, 3] RGB */
+    const uint8_t* joint_color;   /* [num_joints, 3] RGB */
+    float s, X0, Y0, cx, cy;
+    int32_t y_up, z_toward_viewer;
+    float line_width, joint_radius;
+    int32_t height, width;
+    const uint8_t* background;    /* [H, W, 3] or NULL */
+    int64_t background_stride;    /* bytes between the backgrounds of consecutive frames; 0 = one shared */
+    uint8_t background_color[4];  /* RGB (+ pad) where background is NULL */
+    uint8_t* rgb;                 /* [batch, H, W, 3] */
+    void* scratch;
+} dposer_draw_skeletons_args;
+int64_t dposer_draw_skeletons_scratch_bytes(int64_t batch, int32_t num_joints, int32_t num_bones);
+int dposer_draw_skeletons(const dposer_draw_skeletons_args* args, void* stream);
+
+/* Panel compositor -- what lib/utils/motion_video.py:6-55,95-126 does per frame with numpy and cv2 (crop_bottom, cv2.resize,
+ * resize_or_crop, add_title, np.hstack): N output frames [N, out_h, out_w, 3] from num_panels panels each, in one call.  Panel p owns the
+ * output columns [x_offset, x_offset + cell_w) and rows [0, cell_h + strip_h); a later panel overwrites an earlier one where they overlap;
+ * pixels no panel owns take out_fill.  Inside its cell (rows < cell_h), for frame n:
+ *   source  S = src + n * src_stride bytes, uint8 [src_h, src_w, 3] (stride 0: one image shared by every frame);
+ *   crop    C[i][j] = S[crop_y + i][crop_x + j], i < crop_h, j < crop_w;
+ *   resize  R = C when (resize_h, resize_w) == (crop_h, crop_w) (exact byte move).  Otherwise bilinear with cv2.INTER_LINEAR's documented
+ *           geometry, per axis: u = (dst + 0.5) * (crop / resize) - 0.5, i0 = floor(u), f = u - i0, taps i0 and i0 + 1 clamped to
+ *           [0, crop - 1]; value = (1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11) in fp32 (no contraction), stored as rint.
+ *           (cv2's fixed-point path is not reproduced.)
+ *   place   resize_or_crop(R, cell_w, cell_h), each axis on its own: a wider R keeps its centre columns (left = (resize_w - cell_w) / 2), a
+ *           narrower one is centred over fill (left = (cell_w - resize_w) / 2); a taller R keeps its bottom rows, a shorter one is
+ *           bottom-aligned over fill.  (The reference's narrow-and-wrong-height case raises a numpy shape error; here it is defined.)
+ * Rows cell_h <= y < cell_h + strip_h take strip [strip_h, cell_w, 3] (NULL: strip_h must be 0).  At most DPOSER_MAX_PANELS panels.
+ * Every crop must lie inside its source (checked).  Allocates nothing, never synchronises the host. */
+#define DPOSER_MAX_PANELS 8
+typedef struct dposer_panel {
+    const uint8_t* src;           /* [N or 1, src_h, src_w, 3] */
+    int64_t src_stride;           /* bytes between the sources of consecutive frames; 0 = one shared */
+    int32_t src_h, src_w;
+    int32_t crop_x, crop_y, crop_w, crop_h;
+    int32_t resize_h, resize_w;
+    int32_t cell_h, cell_w;
+    uint8_t fill[4];              /* RGB (+ pad) */
+    const uint8_t* strip;         /* [strip_h, cell_w, 3] or NULL */
+    int32_t strip_h;
+    int32_t x_offset;
+} dposer_panel;
+typedef struct dposer_compose_args {
+    const dposer_panel* panels;   /* host array [num_panels] */
+    int32_t num_panels;
+    int64_t num_frames;
+    int32_t out_h, out_w;
+    uint8_t out_fill[4];          /* RGB (+ pad) */
+    uint8_t* out;                 /* [num_frames, out_h, out_w, 3] */
+} dposer_compose_args;
+int dposer_compose_panels(const dposer_compose_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
