@@ -483,6 +483,127 @@ hipError_t launch_denoise(const DenoiseArgs& a, int* nblocks, hipStream_t st) {
     return hipGetLastError();
 }
 
+// One step of multi_step_denoise (run/completion.py:112-129, smplify.py:76-92, motion_denoising.py:106-122) behind the network evaluation at
+// time_traj[i]:   noise = -score * sigma_c;   x = alpha_b / alpha_c * (x - sigma_c * noise) + sigma_b * noise
+// in the reference's operation order, (alpha, sigma) = return_alpha_sigma at time_traj[i] (c) and time_traj[i + 1] (b).  The state is read
+// and written as fp32 rows (xt) and re-tiled for the next GEMM (xin; padded rows / columns are zeros, as k_perturb_shared writes them).  The
+// LAST step writes no state: the same pass forms x0_hat, the gradient 2 w (x0 - x0_hat) inv_n and the block partials of the loss
+// (completion.py:142-147; w from the SNR alpha / sigma at time_traj[0], :127-128).
+struct DdimDev {
+    DdimStepArgs a;
+    SdeDev sde;
+};
+template <typename T> __global__ void __launch_bounds__(256) k_ddim_step(DdimDev d) {
+    const DdimStepArgs& a = d.a;
+    const int qx = a.Dpad >> 2;
+    const SdeAt at = sde_at(d.sde, a.t);
+    const SdeAt ab = sde_at(d.sde, a.t_next);
+    const float a_c = at.mc, s_c = at.sd, s_b = ab.sd;               // return_alpha_sigma, sde_lib.py:177-181 / :227-231 / :289-292
+    const float ratio = ab.mc / a_c;
+    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    float w = 0.5f;
+    if (a.last && a.weighted) {
+        const SdeAt a0 = sde_at(d.sde, a.t0);
+        w = 0.5f * sqrtf(1.0f + a0.mc / a0.sd);                       // completion.py:128,143
+    }
+    float acc = 0.f;
+    const int64_t total = a.Bpad * qx;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qx;
+        const int c = (int)(i % qx) * 4;
+        f32x4 xn = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+            const f32x4 r4 = *reinterpret_cast<const f32x4*>(a.res + s * a.Cp + c);
+            const f32x4 x4 = *reinterpret_cast<const f32x4*>(a.xt + s * a.Dpad + c);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const float model = r4[r] / usig;
+                const float score = sde_score(d.sde, model, at.sd_score);     // utils.py:155,162 / :160 / :180
+                const float noise = -score * s_c;                             // completion.py:122
+                const float x = ratio * (x4[r] - s_c * noise) + s_b * noise;  // :123-126
+                xn[r] = x;
+                if (a.last) {
+                    const int64_t o = s * a.D + c + r;
+                    const float diff = a.x0[o] - x;
+                    acc += w * (diff * diff);
+                    if (a.x0_hat) a.x0_hat[o] = x;
+                    if (a.grad) a.grad[o] = (2.0f * w) * diff * a.inv_n;
+                }
+            }
+        }
+        if (!a.last) {
+            store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
+            *reinterpret_cast<f32x4*>(a.xt + s * a.Dpad + c) = xn;
+        }
+    }
+    if (a.last) {
+        const float tot = block_sum_256(acc);
+        if (threadIdx.x == 0) a.loss_part[blockIdx.x] = tot * a.inv_n;
+    }
+}
+hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st) {
+    DdimDev d;
+    d.a = a;
+    d.sde = make_sde_dev_at(a.sde, a.t);
+    const int g = grid_for(a.Bpad * (a.Dpad >> 2), 256, a.last ? 1024 : 8192);      // (last step: one partial per block, as k_denoise)
+    *nblocks = g;
+    if (a.f32) hipLaunchKernelGGL(k_ddim_step<float>, dim3(g), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(k_ddim_step<__bf16>, dim3(g), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+
+// MotionDenoise.RED_Diff (run/motion_denoising.py:145-154) behind the network evaluation at x_t = mean + std z:
+//   eps_pred = -score * std;   weight = sqrt(sigma^2) / alpha;   guidance = mean_b(weight * <(eps_pred - z).detach(), x_0>)
+// and its gradient weight (eps_pred - z) / B w.r.t. x_0.  z is the perturbation's: the injected array, or the Philox draws of
+// k_perturb_shared regenerated from the same counters.  One quad per thread, block partials in a fixed order: no float atomics.
+struct RedDiffDev {
+    RedDiffArgs a;
+    SdeDev sde;
+};
+__global__ void __launch_bounds__(256) k_red_diff(RedDiffDev d) {
+    const RedDiffArgs& a = d.a;
+    const int QD = (a.D + 3) >> 2;
+    const SdeAt at = sde_at(d.sde, a.t);
+    const float alpha = at.mc, sigma = at.sd;                         // return_alpha_sigma; marginal_prob's std is the same number
+    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float weight = sqrtf(sigma * sigma) / alpha;                // motion_denoising.py:151-152
+    float acc = 0.f;
+    const int64_t total = a.B * QD;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / QD;
+        const int q = (int)(i % QD);
+        const int c = q * 4;
+        float n4[4];
+        if (!a.z_in) normals4((uint64_t)s * QD + q, STREAM_PRIOR, a.step, a.seed, n4);
+        const f32x4 r4 = *reinterpret_cast<const f32x4*>(a.res + s * a.Cp + c);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (c + r >= a.D) continue;
+            const int64_t o = s * a.D + c + r;
+            const float z = a.z_in ? a.z_in[o] : n4[r];
+            const float model = r4[r] / usig;
+            const float score = sde_score(d.sde, model, at.sd_score);
+            const float eps = -score * sigma;                         // :150 score to noise prediction
+            const float dz = eps - z;
+            acc += dz * a.x0[o];
+            if (a.eps_pred) a.eps_pred[o] = eps;
+            if (a.grad) a.grad[o] = (weight * dz) * a.inv_batch;
+        }
+    }
+    const float tot = block_sum_256(acc);
+    if (threadIdx.x == 0) a.loss_part[blockIdx.x] = (weight * tot) * a.inv_batch;
+}
+hipError_t launch_red_diff(const RedDiffArgs& a, int* nblocks, hipStream_t st) {
+    RedDiffDev d;
+    d.a = a;
+    d.sde = make_sde_dev_at(a.sde, a.t);
+    const int g = grid_for(a.B * ((a.D + 3) >> 2), 256, 1024);
+    *nblocks = g;
+    hipLaunchKernelGGL(k_red_diff, dim3(g), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+
 // One step of DPoserComp.optimize behind the network evaluation: Tweedie estimate (completion.py:105-110), gradient of
 //   w_prior * mean(w (x - x0_hat)^2) + w_data * MSE(x * mask, obs * mask)                (completion.py:131-149,195-201)
 // w.r.t. x (x0_hat is detached in the reference), and torch.optim.Adam's update of x with per-element moments -- one pass

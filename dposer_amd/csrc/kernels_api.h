@@ -140,6 +140,44 @@ struct PerturbSharedArgs { // x_t = mean + std*z at one shared t; writes xin (FT
 };
 hipError_t launch_perturb_shared(const PerturbSharedArgs& a, hipStream_t st);
 
+struct DdimStepArgs {      // one step of multi_step_denoise behind its network evaluation (run/completion.py:112-129); the last step also forms the loss
+    const float* res;      // [Bpad][Cp] model output at x_t
+    float* xt;             // [Bpad][Dpad] current state (fp32 row-major), updated in place
+    void* xin;             // FT [Bpad][Dpad]: the next evaluation's network input
+    const float* sigmas;
+    const float* x0;       // last step: [B][D] clean poses
+    float* x0_hat;         // last step: [B][D] the multi-step estimate, or null
+    float* grad;           // last step: [B][D] d loss / d x0 (the estimate is detached) or null
+    float* loss_part;      // last step: per-block partial sums
+    float t, t_next;       // time_traj[i], time_traj[i + 1]
+    float t0;              // time_traj[0]: the SNR of the loss weight (completion.py:127-128)
+    float inv_n;
+    int weighted;
+    int last;              // 1: no state is written back; x0_hat / grad / loss_part are
+    int64_t B, Bpad;
+    int D, Dpad, Cp, num_scales, scale_by_sigma, f32;
+    SdeCfg sde;
+};
+hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st);
+
+struct RedDiffArgs {       // MotionDenoise.RED_Diff behind its network evaluation (run/motion_denoising.py:145-154)
+    const float* res;      // [Bpad][Cp] model output at x_t
+    const float* x0;       // [B][D]
+    const float* z_in;     // the perturbation's injected z, or null (-> the same Philox STREAM_PRIOR draws as k_perturb_shared)
+    const float* sigmas;
+    float* eps_pred;       // [B][D] noise prediction -score * std, or null
+    float* grad;           // [B][D] weight (eps_pred - z) inv_batch, or null
+    float* loss_part;      // per-block partial sums
+    float t;
+    float inv_batch;
+    int64_t B;
+    int D, Cp, num_scales, scale_by_sigma;
+    SdeCfg sde;
+    uint64_t seed;
+    uint32_t step;
+};
+hipError_t launch_red_diff(const RedDiffArgs& a, int* nblocks, hipStream_t st);
+
 struct CompletionUpdateArgs {   // one optimisation step of DPoserComp.optimize (run/completion.py:167-207) after the network evaluation
     const float* res;      // [Bpad][Cp] model output at x_t
     const float* xt;       // [Bpad][Dpad] perturbed data

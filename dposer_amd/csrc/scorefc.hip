@@ -856,6 +856,8 @@ static SdeCfg to_sde(const dposer_sde_desc* s) {
 static bool sde_kind_ok(const dposer_sde_desc* s) {
     return s->kind == DPOSER_SDE_SUBVP || s->kind == DPOSER_SDE_VP || s->kind == DPOSER_SDE_VE || s->kind == DPOSER_SDE_VE_DISCRETE || s->kind == DPOSER_SDE_VP_DISCRETE;
 }
+// (the multi-step and RED-Diff prior entries: verified against the reference for the continuous score functions only)
+static bool sde_kind_continuous(const dposer_sde_desc* s) { return s->kind == DPOSER_SDE_SUBVP || s->kind == DPOSER_SDE_VP || s->kind == DPOSER_SDE_VE; }
 // What the network is conditioned on at the n step times `t_host`, into w.tt_labels: t * 999 (utils.py:152: one IEEE fp32 product, the same
 // bits on host and device) or, for VE, sigma(t) (utils.py:173) -- formed ON THE DEVICE from the staged times (k_ve_labels), because every
 // kernel that perturbs with sigma(t) / divides the output by it calls the device's powf, and the host's libm may round the last bit the other way.
@@ -1150,6 +1152,78 @@ extern "C" int dposer_prior_loss_tabled(dposer_scorefc_t h, const float* flat, c
     DP_CHECK_ARG(table_rows >= 1, "table_rows must be >= 1");
     return prior_loss_impl(h, flat, packed_, ws_, sde, x0, z, t, weighted, inv_n, x0_hat, grad, loss, seed, step, nullptr, sigmas, B, stream, row,
                            table_rows);
+}
+
+// The prior loss on the MULTI-STEP estimate (multi_denoise = True: run/completion.py:112-149, smplify.py:76-107, motion_denoising.py:106-143):
+// the time-bias rows of all n_steps evaluations are built in one pass, then perturb at time_traj[0] and, per step, one network evaluation +
+// k_ddim_step; the last step's launch forms x0_hat, gradient and loss partials.  1 + n_steps (network + 1) + 1 launches behind the table.
+extern "C" int dposer_prior_loss_multi(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                       const float* x0, const float* z, const float* t_traj_host, int32_t n_steps, int32_t weighted,
+                                       float inv_n, float* x0_hat, float* grad, float* loss, uint64_t seed, uint32_t step, const float* freq,
+                                       const float* sigmas, int64_t B, void* stream) {
+    DP_RANGE();
+    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    g_alg_batch = B;
+    DP_CHECK_ARG(n_steps >= 1 && n_steps <= 64, "n_steps must be in 1..64");
+    DP_CHECK_ARG(t_traj_host, "t_traj_host is null (n_steps + 1 host floats)");
+    DP_CHECK_ARG(sde && x0 && loss && freq && sigmas, "null argument");
+    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
+    DP_CHECK_ARG(sde_kind_continuous(sde), "continuous score functions only (sub-VP, VP, VE): the discrete kinds are not verified for this entry");
+    hipStream_t st = (hipStream_t)stream;
+    const char* packed = (const char*)packed_;
+    Ws w;
+    layout_ws(h, B, DPOSER_WS_SHARED_T, n_steps, (char*)ws_, w);
+    DP_TRY(stage_step_labels(h, w, sde, t_traj_host, n_steps, st));      // the network is evaluated at time_traj[0 .. n_steps - 1]
+    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_steps, freq, st));
+    const SdeCfg sc = to_sde(sde);
+    PerturbSharedArgs pa;
+    pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t_traj_host[0]; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
+    pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
+    DP_HIP_LAUNCH(launch_perturb_shared(pa, st));
+    DdimStepArgs da;
+    da.res = w.res; da.xt = w.xt; da.xin = w.xin; da.sigmas = sigmas; da.x0 = x0; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = w.loss_part;
+    da.t0 = t_traj_host[0]; da.inv_n = inv_n; da.weighted = weighted; da.B = B; da.Bpad = w.Bpad; da.D = h->D; da.Dpad = h->Dpad; da.Cp = h->Cp;
+    da.num_scales = h->d.num_scales; da.scale_by_sigma = sbs_mode(h); da.f32 = h->f32; da.sde = sc;
+    int nb = 0;
+    for (int i = 0; i < n_steps; ++i) {
+        DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+        da.t = t_traj_host[i]; da.t_next = t_traj_host[i + 1]; da.last = i + 1 == n_steps;
+        DP_HIP_LAUNCH(launch_ddim_step(da, &nb, st));
+    }
+    DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, loss, st));
+    return DPOSER_OK;
+}
+
+// MotionDenoise.RED_Diff (run/motion_denoising.py:145-154): perturb, one network evaluation, k_red_diff (noise prediction, guidance scalar and
+// its gradient w.r.t. x0 -- the residual is detached in the reference).
+extern "C" int dposer_prior_red_diff(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                     const float* x0, const float* z, float t, float inv_batch, float* eps_pred, float* grad, float* loss,
+                                     uint64_t seed, uint32_t step, const float* freq, const float* sigmas, int64_t B, void* stream) {
+    DP_RANGE();
+    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    g_alg_batch = B;
+    DP_CHECK_ARG(sde && x0 && loss && freq && sigmas, "null argument");
+    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
+    DP_CHECK_ARG(sde_kind_continuous(sde), "continuous score functions only (sub-VP, VP, VE): the discrete kinds are not verified for this entry");
+    hipStream_t st = (hipStream_t)stream;
+    const char* packed = (const char*)packed_;
+    Ws w;
+    layout_ws(h, B, DPOSER_WS_SHARED_T, 1, (char*)ws_, w);
+    DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
+    const SdeCfg sc = to_sde(sde);
+    PerturbSharedArgs pa;
+    pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
+    pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
+    DP_HIP_LAUNCH(launch_perturb_shared(pa, st));
+    DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
+    RedDiffArgs ra;
+    ra.res = w.res; ra.x0 = x0; ra.z_in = z; ra.sigmas = sigmas; ra.eps_pred = eps_pred; ra.grad = grad; ra.loss_part = w.loss_part;
+    ra.t = t; ra.inv_batch = inv_batch; ra.B = B; ra.D = h->D; ra.Cp = h->Cp; ra.num_scales = h->d.num_scales; ra.scale_by_sigma = sbs_mode(h);
+    ra.sde = sc; ra.seed = seed; ra.step = step;
+    int nb = 0;
+    DP_HIP_LAUNCH(launch_red_diff(ra, &nb, st));
+    DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, loss, st));
+    return DPOSER_OK;
 }
 
 // DPoserComp.optimize (run/completion.py:167-207): the whole optimisation loop in one call.  Per step: perturb x at the step's

@@ -29,11 +29,13 @@ class DPoserComp:
         self.data_loss = nn.MSELoss(reduction="mean")
         self._calls = 0
 
-    def loss(self, x_0, t, weighted=False, z=None):
-        """completion.py:131-149 at one shared time ``t`` (python float): mean(weight * (x_0 - x0_hat)^2)."""
+    def loss(self, x_0, t, weighted=False, z=None, multi_denoise=False):
+        """completion.py:131-149 at one shared time ``t`` (python float): mean(weight * (x_0 - x0_hat)^2).  ``multi_denoise=True``: x0_hat
+        from 10 DDIM steps down to t / 20 (completion.py:138) -- one ``dposer_prior_loss_multi`` call where ``prior_loss`` fuses it."""
         self._calls += 1
         return prior_loss(self.model, self.sde, x_0, t, weighted=bool(weighted), reduction="mean", z=z,
-                          seed=self.model._rng_seed + 29, step=self._calls, continuous=bool(getattr(self, "continuous", True)))
+                          seed=self.model._rng_seed + 29, step=self._calls, continuous=bool(getattr(self, "continuous", True)),
+                          **({"multi_denoise": 10} if multi_denoise else {}))      # (off: today's call, argument for argument)
 
     def get_loss_weights(self):
         """completion.py:151-155."""

@@ -22,7 +22,7 @@ import torch
 
 from .. import _C
 from ..algorithms.advanced import sde_lib
-from ..prior import prior_loss
+from ..prior import prior_loss, red_diff
 from ..utils.misc import gaussian_smoothing
 
 
@@ -87,11 +87,20 @@ class MotionDenoise:
         self.model = diffusion_model
         self._calls = 0
 
-    def DPoser_loss(self, x_0, t, weighted=False, z=None):
-        """motion_denoising.py:124-143: sum(weight * (x_0 - x0_hat)^2) / batch_size."""
+    def DPoser_loss(self, x_0, t, weighted=False, z=None, multi_denoise=False):
+        """motion_denoising.py:124-143: sum(weight * (x_0 - x0_hat)^2) / batch_size.  ``multi_denoise=True``: x0_hat from 10 DDIM steps
+        down to t / 20 (:132) -- one ``dposer_prior_loss_multi`` call where ``prior_loss`` fuses it."""
         self._calls += 1
         return prior_loss(self.model, self.sde, x_0, t, weighted=weighted, reduction="sum_over_batch", batch_size=self.batch_size, z=z,
-                          seed=self.model._rng_seed + 31, step=self._calls, continuous=getattr(self, "continuous", True))
+                          seed=self.model._rng_seed + 31, step=self._calls, continuous=getattr(self, "continuous", True),
+                          **({"multi_denoise": 10} if multi_denoise else {}))      # (off: today's call, argument for argument)
+
+    def RED_Diff(self, x_0, t, z=None):
+        """motion_denoising.py:145-154: mean_b(sigma / alpha * <(eps_pred - z).detach(), x_0>) at one shared time ``t`` -- one
+        ``dposer_prior_red_diff`` call where ``red_diff`` fuses it."""
+        self._calls += 1
+        return red_diff(self.model, self.sde, x_0, t, z=z, seed=self.model._rng_seed + 31, step=self._calls,
+                        continuous=getattr(self, "continuous", True))
 
     def get_loss_weights(self):
         """motion_denoising.py:157-163."""

@@ -177,6 +177,27 @@ int dposer_prior_loss_tabled(dposer_scorefc_t h, const float* flat_params, const
                              float* x0_hat, float* grad, float* loss, uint64_t seed, uint32_t step, const float* sigmas,
                              int64_t batch, void* stream);
 
+/* The prior loss on the MULTI-STEP estimate -- multi_step_denoise and the multi_denoise = True branch of the loss:
+ * run/smplify.py:76-107, run/completion.py:112-149, run/motion_denoising.py:106-143, run/demo.py:251-288.  n_steps (1..64) deterministic
+ * DDIM steps  noise = -score * sigma_c;  x = alpha_b / alpha_c * (x - sigma_c * noise) + sigma_b * noise  along
+ *   t_traj_host [n_steps + 1], HOST: the reference's time grid linear_interpolation(t, t_end, n_steps + 1) (lib/utils/misc.py:58-61);
+ * the network is evaluated at t_traj_host[0 .. n_steps - 1] (their time-bias rows built in one pass), the perturbation and the SNR of the
+ * weight 0.5 sqrt(1 + alpha / sigma) (completion.py:127-128,142-145) are those of t_traj_host[0].  x0_hat [B, D] = the final state (or NULL);
+ * grad = 2 w (x0 - x0_hat) inv_n (the estimate is detached) or NULL; the other arguments as dposer_prior_loss.
+ * Workspace: DPOSER_WS_SHARED_T with n_steps table rows.  DPOSER_SDE_SUBVP / _VP / _VE only (this entry and dposer_prior_red_diff refuse the
+ * discrete kinds: the Python surface composes those from the HIP score function). */
+int dposer_prior_loss_multi(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws, const dposer_sde_desc* sde,
+                            const float* x0, const float* z, const float* t_traj_host, int32_t n_steps, int32_t weighted, float inv_n,
+                            float* x0_hat, float* grad, float* loss, uint64_t seed, uint32_t step, const float* freq, const float* sigmas,
+                            int64_t batch, void* stream);
+/* MotionDenoise.RED_Diff -- run/motion_denoising.py:145-154: perturb x0 at the shared time t, one network evaluation, then
+ *   eps_pred = -score * std,  weight = sigma / alpha,  loss [1] = inv_batch * sum_b weight * sum_j (eps_pred - z)[b, j] * x0[b, j],
+ *   grad [B, D] = weight * (eps_pred - z) * inv_batch  (the residual is detached in the reference), or NULL;  eps_pred [B, D] or NULL.
+ * z [B, D] injected noise or NULL -> Philox(seed, step), the draws dposer_prior_loss makes.  Workspace: DPOSER_WS_SHARED_T, one row. */
+int dposer_prior_red_diff(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws, const dposer_sde_desc* sde,
+                          const float* x0, const float* z, float t, float inv_batch, float* eps_pred, float* grad, float* loss,
+                          uint64_t seed, uint32_t step, const float* freq, const float* sigmas, int64_t batch, void* stream);
+
 /* ---- TimeMLPs (lib/algorithms/advanced/model.py:69-90): the reference's secondary score model -------------------------------------
  *   net = Linear(in_dim, H), act, [Linear(H, H), act, Dropout(p)] x n_blocks, Linear(H, out_dim)      (in_dim = data_dim + 1: [x, t])
  * Flat parameter buffer: net.parameters() in order (weight [out][in] row-major, bias) per Linear, contiguous fp32.  Every Linear + act
