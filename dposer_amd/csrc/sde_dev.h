@@ -48,20 +48,25 @@ static inline SdeDev make_sde_dev(const SdeCfg& s) {
     }
     return d;
 }
-// VPSDE.sqrt_1m_alphas_cumprod[k] (sde_lib.py:134-139): discrete_betas = linspace(beta_min / N, beta_max / N, N) as torch forms it in fp32 (from both
-// ends: start + step i below the middle, end - step (N - 1 - i) above), alphas = 1 - betas, a running fp32 product, sqrt(1 - product)
+// VPSDE.sqrt_1m_alphas_cumprod[k] (sde_lib.py:134-139): discrete_betas = linspace(beta_min / N, beta_max / N, N), alphas = 1 - betas in fp32,
+// torch.cumprod -- which on the CPU accumulates an fp32 tensor in double and rounds each entry to fp32 -- and sqrt(1 - cumprod) in fp32.
+// The product therefore runs in double here: an fp32 running product loses 2^-24 per factor against 1 - product ~ 1e-4 k at small k.
+// The betas are linspace's two-ended fp32 formula (start + step i below the middle, end - step (N - 1 - i) above).  torch's vectorised
+// kernel can differ from that by an ulp of beta, which is far below the rounding of 1 - beta, so the table is close to torch's but not
+// bit-equal to it; the reference's own tables and the bound held against them are in tests/ (golden g27).
 static inline float sde_vp_sqrt_1m_alphas_cumprod(const SdeCfg& s, int k) {
+#pragma clang fp contract(off)
     const int N = s.N;
     if (N < 1) return 0.f;
     k = k < 0 ? 0 : (k >= N ? N - 1 : k);
     const float start = (float)(s.beta_0 / (double)N), end = (float)(s.beta_1 / (double)N);
     const float step = N > 1 ? (end - start) / (float)(N - 1) : 0.f;
-    float prod = 1.0f;
+    double prod = 1.0;
     for (int i = 0; i <= k; ++i) {
         const float beta = i < N / 2 ? start + step * (float)i : end - step * (float)(N - 1 - i);
-        prod = prod * (1.0f - beta);
+        prod = prod * (double)(1.0f - beta);
     }
-    return sqrtf(1.0f - prod);
+    return sqrtf(1.0f - (float)prod);
 }
 // the descriptor of a launch at ONE shared time t: for the discrete VP score function the table entry travels by value
 static inline SdeDev make_sde_dev_at(const SdeCfg& s, float t) {
