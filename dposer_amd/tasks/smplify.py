@@ -67,7 +67,12 @@ class SMPLify:
     """run/smplify.py:118-281.  ``pose_prior``: a ``prior.DPoser`` to use instead of building one from ``args`` (e.g.
     ``DPoser(model=..., normalizer=...)`` over an in-memory network).  ``__call__`` returns (pose [B, 66], betas, camera_translation,
     reprojection_loss [B, 49]) like the reference; ``fused`` / ``noise`` [n_stages * num_iters, B, network inputs] / ``seed`` are this
-    repository's keywords."""
+    repository's keywords.
+
+    ``loss_log`` (after a fused call): [num_iters * (1 + stages), B, 4], every iteration's loss terms per image as they enter the loss --
+    camera rows (camera loss, 0, 0, depth term), body rows (reprojection, angle prior, shape prior, pose prior).  The pose prior is one
+    scalar per C call: each image's row carries w_pose^2 * (sum over the images of ITS GROUP) / B.  One group (any B up to 65535) logs
+    the loss's own sum / batch_size term in every row; with more groups the groups' values add up to that term."""
 
     def __init__(self, body_model, step_size=1e-2, batch_size=32, num_iters=100, focal_length=5000, args=None, pose_prior=None):
         from ..body_model.smpl import SMPLX

@@ -650,7 +650,10 @@ int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* args, void*
  *   t_host [n_stages * num_iters]; w_pose_host / w_shape_host / w_angle_host [n_stages]: HOST arrays.
  *   scratch: dposer_smplify_scratch_bytes(batch, V, J, joint_rows, num_shape, network inputs) bytes, 256-byte aligned.
  *   loss_log: DEVICE [num_iters * (1 + n_stages), batch, 4] or NULL: camera rows (camera loss, 0, 0, depth term), body rows (reprojection,
- *   angle, shape, prior) weighted as they enter the loss; the prior entry is the batch's sum / batch_size term.
+ *   angle, shape, prior) weighted as they enter the loss.  Columns 0-2 (and the camera rows) are per image and do not depend on how a
+ *   larger problem is split into calls.  The prior entry is the one per-call quantity: w_pose^2 * inv_batch * (sum over THIS call's
+ *   `batch` images), the same value in every image's row -- one call over the whole problem logs the loss's sum / batch_size term, and the
+ *   entries of the calls a problem is split into add up to it.
  * Allocates nothing, never synchronises the host. */
 typedef struct dposer_smplify_args {
     dposer_scorefc_t net;
