@@ -111,7 +111,8 @@ template <bool IEEE> __global__ void __launch_bounds__(256) k_md_vert_grad(const
 
 // data term (:257-263) and the step's loss log.  One block: pass 1 = mean distance (decides whether the term is kept: finite
 // and > 0, the reference's `if data_term > 0`), pass 2 = gradient rows.  Distances are clamped at 1e-18 before the division: a
-// zero residual contributes the value ~0 and a zero gradient (sqrt'(0) = inf would poison the backward pass).
+// zero residual contributes the value ~0 and a zero gradient (sqrt'(0) = inf would poison the backward pass).  A NaN residual is not
+// clamped: it makes the sequence's mean NaN, and the whole term of that sequence is dropped for the step, as in the reference.
 __global__ void __launch_bounds__(256) k_md_joint(const float* joints, int64_t ld, const float* obs, float* djoints, int T, int n_obs, float w_data,
                                                   const float* temp_part, int n_temp_part, float temp_scale, const float* prior_loss, float* log3) {
     // (n_temp_part = 0: the temporal term's distance sums do not exist yet -- k_md_temp_log writes log3[0] behind the LBS backward)
@@ -127,7 +128,8 @@ __global__ void __launch_bounds__(256) k_md_joint(const float* joints, int64_t l
         const float* a = joints + (int64_t)t * ld + j * 3;
         const float* o = obs + (int64_t)e * 3;
         const float dx = a[0] - o[0], dy = a[1] - o[1], dz = a[2] - o[2];
-        acc += sqrtf(fmaxf(dx * dx + dy * dy + dz * dz, 1e-36f));
+        const float s = dx * dx + dy * dy + dz * dz;
+        acc += sqrtf(s < 1e-36f ? 1e-36f : s);      // (not fmaxf: it returns 1e-36 for a NaN, and the sequence's term must become NaN to be dropped)
     }
     const float mean = block_sum(acc, red) / (float)n;
     const bool keep = isfinite(mean) && mean > 0.f;

@@ -184,6 +184,7 @@ class MotionDenoise:
             lr=0.03, beta1=0.9, beta2=0.999, eps=1e-8, adam_step0=0, step0=int(step0) & 0xFFFFFFFF, seed=int(model._rng_seed + 31),
             noise=_C.ptr(nzs), scratch=_C.ptr(scratch), loss_log=_C.ptr(log), rot6d=1 if rot6d else 0)
         _C.check(lib.dposer_motion_denoise_optimize(C.byref(a), _C.stream_ptr()), "dposer_motion_denoise_optimize")
+        self.adam_state = (m, v)                                   # torch.optim.Adam's exp_avg / exp_avg_sq after the last step (of the last call), [T, 63]
         return log
 
     def _quan_t(self, time_strategy, step, total_steps, sample_trun, sample_time):
@@ -217,7 +218,8 @@ class MotionDenoise:
             return out
         bm = self.body_model
         flat = lambda x: x.reshape(S * F, *x.shape[2:])
-        betas = self.betas[:1].expand(S * F, -1).contiguous()
+        # (the body shapes the loop itself uses, _optimize_fused: one per frame of the batch if the module holds S * F of them)
+        betas = self.betas if self.betas.shape[0] == S * F else self.betas[:1].expand(S * F, -1).contiguous()
         with torch.no_grad():
             gt = bm(betas=betas, pose_body=flat(gt_poses))
             je = flat(joints3d) - gt.Jtr[:, :22]

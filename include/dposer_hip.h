@@ -554,7 +554,8 @@ int dposer_lbs_backward(dposer_body_t h, const void* ws_fwd, void* ws_bwd, const
  *   w_temp[i] * mean ||v[t] - v[t+1]|| + w_data[i] * mean ||Jtr[:, :n_obs_joints] - joints_obs|| + w_prior[i] * DPoser_loss(normalise(pose)),
  * all steps queued from one call (prior evaluation = dposer_prior_loss, body model = dposer_lbs_forward / _backward, the
  * loss gradients and the Adam update are kernels of this entry).  The data term is dropped for a step when its value is not
- * finite and > 0 (:261-263) -- decided on the device.
+ * finite and > 0 (:261-263) -- decided on the device, per sequence: one NaN among a sequence's observed joints drops that
+ * sequence's whole term for the step (and logs it as 0), as the reference's guard does; the other sequences are unaffected.
  *   score network: handle, parameters, packed weights, a DPOSER_WS_SHARED_T workspace for `frames` samples and n_steps table rows;
  *   body model: handle + the device tables dposer_lbs_forward / dposer_lbs_backward take, their two workspaces for `frames`
  *   poses; rest_batched: v_shaped / j_rest are [frames, ...] instead of shared; pose segments other than `body_segment` are

@@ -28,12 +28,13 @@ def sigma_table(sigma_min=0.01, sigma_max=50.0, num_scales=1000) -> torch.Tensor
     return torch.tensor(s, dtype=torch.float)
 
 
-def timestep_embedding(labels: torch.Tensor, dim: int, max_positions=10000) -> torch.Tensor:
-    """lib/algorithms/advanced/model.py:37-51 (sinusoidal embedding of the labels t*999)."""
+def timestep_embedding(labels: torch.Tensor, dim: int, max_positions=10000, dtype=torch.float32) -> torch.Tensor:
+    """lib/algorithms/advanced/model.py:37-51 (sinusoidal embedding of the labels t*999).  ``dtype``: what integer labels are converted to
+    (float32 in the reference; the float64 loops of oracle/task_loops.py embed them in float64)."""
     half = dim // 2
     scale = math.log(max_positions) / (half - 1)
     if not labels.is_floating_point():
-        labels = labels.float()                                                # model.py:46 `timesteps.float()` (integer labels: the discrete score functions)
+        labels = labels.to(dtype)                                              # model.py:46 `timesteps.float()` (integer labels: the discrete score functions)
     freq = torch.exp(torch.arange(half, dtype=torch.float32) * -scale).to(labels.dtype)
     arg = labels[:, None] * freq[None, :]
     emb = torch.cat([torch.sin(arg), torch.cos(arg)], dim=1)
@@ -87,7 +88,7 @@ def scorefc_forward(p: Params, batch: torch.Tensor, labels: torch.Tensor, *, n_b
         temb = fourier_embedding(torch.log(used_sigmas), p["gauss_proj.W"])    # model.py:153
     elif embedding_type == "positional":
         used_sigmas = p["sigmas"].to(batch.dtype)[labels.long()]               # model.py:159
-        temb = timestep_embedding(labels, embed_dim)                           # model.py:160
+        temb = timestep_embedding(labels, embed_dim, dtype=batch.dtype)        # model.py:160
     else:
         raise ValueError(embedding_type)
     temb = silu(_lin(p, "shared_time_embed.0", temb))                          # model.py:164

@@ -4,7 +4,10 @@
                                :151-155 and ``backward_step`` :157-165.
 * ``motion_denoise_optimize``  run/motion_denoising.py:199-300 (``MotionDenoise.optimize``) with ``DPoser_loss`` :124-143, the
                                weights of :157-163, the ``if data_term > 0`` guard :261-263 and the final Gaussian smoothing
-                               (lib/utils/misc.py:84-95).
+                               (lib/utils/misc.py:84-95).  Its defaults are the loop golden g15 pins; with ``dtype=torch.float64``
+                               it is the arbiter of the one-call loop in every configuration that loop takes (normalisers, rot6d,
+                               SDE kinds, embeddings, batches of sequences, per-frame betas), step by step and term by term
+                               (tests/motion_denoise_cases.py, tests/test_motion_denoise_ref_cpu.py, tests/test_gpu_motion_denoise.py).
 
 * ``smplify_optimize``         run/smplify.py:182-281 (``SMPLify.__call__``) with the losses of lib/body_model/fitting_losses.py:6-131,
                                the prior of run/smplify.py:93-115 and the stage weights of :145-149 -- float64 by default, the
@@ -67,54 +70,152 @@ def gaussian_smoothing(x, window_size=3, sigma=2.0):
     return out[0].t()
 
 
+# the faults ``motion_denoise_optimize(fault=...)`` can seed into itself: tests/test_motion_denoise_ref_cpu.py shows that each one leaves
+# the comparison band of tests/test_gpu_motion_denoise.py, i.e. that a kernel with that defect could not pass
+MOTION_DENOISE_FAULTS = ("temporal_crosses_sequences", "temporal_mean_over_T", "data_guard_ignored", "data_mean_over_frames", "min_max_without_2",
+                         "prior_grad_not_divided_by_std", "rot6d_grad_not_through_rodrigues", "prior_weight_of_previous_iteration",
+                         "noise_row_shifted", "weighted_on")
+
+
 def motion_denoise_optimize(p, sde, asset, mean, std, joints3d, gt_poses, init_poses, noise, *, iterations=5, steps_per_iter=50,
-                            sample_trun=2.0, dposer_weight=1.0, body_dtype=torch.float64):
-    """run/motion_denoising.py:199-300, time strategy '3', z-score normaliser.  Returns (final pose_body before smoothing,
-    {'init_MPJPE', 'MPJPE', 'MPVPE'}).  The body model is fk_torch (float64; ``body_dtype=torch.float32`` = the precision smplx runs in inside the reference); poses are an fp32 leaf like in the reference."""
+                            sample_trun=2.0, dposer_weight=1.0, body_dtype=torch.float64, dtype=None, norm_mode="zscore", rot6d=False,
+                            embedding_type="positional", weighted=False, time_strategy="3", sample_time=990, betas=None, n_obs_joints=22,
+                            frames_per_sequence=None, fault=None, details=False):
+    """run/motion_denoising.py:199-300.  With the defaults: time strategy '3', z-score normaliser, returns (final pose_body before
+    smoothing, {'init_MPJPE', 'MPJPE', 'MPVPE'}); the body model is fk_torch (float64; ``body_dtype=torch.float32`` = the precision smplx
+    runs in inside the reference), poses are an fp32 leaf and the network runs in fp32 like in the reference -- the loop golden g15 pins.
+
+    ``dtype``: None = that mixed loop; torch.float64 / torch.float32 = EVERYTHING in that precision -- network, body model, pose leaf,
+    Adam: float64 is the arbiter of the one-call loop, float32 sizes the reference's own rounding.
+    ``norm_mode``: None / 'none', 'zscore' (``mean``, ``std`` = the statistics) or 'minmax' (``mean``, ``std`` = min, max);  ``rot6d``: the
+    network sees the 6 J coordinates of ``smplify_normalize`` and its gradient returns through autograd of that conversion (noise and
+    statistics are 6 J wide);  the SDE kind is ``sde`` (R.SubVP / R.VP / R.VE, ``discrete=True`` for the discrete score functions);
+    ``embedding_type``: 'positional' or 'fourier';  ``weighted``: DPoser_loss's flag (:124, False in the reference);  ``time_strategy``
+    '2' (the fixed ``sample_time``) or '3';  ``betas`` [frames, 10] or [1, 10]: body shapes (None: zeros);  ``n_obs_joints``: the first
+    joints the data term (and init_MPJPE) reads.
+    ``frames_per_sequence`` F: the frames are S = frames / F sequences of F consecutive frames, S independent problems: every loss
+    term, its mean, the ``data_term > 0`` decision and the prior (``sum_over_batch`` with batch_size = F, what one sequence alone gets) are
+    formed on the sequence's slice; Adam is element-wise, so this IS S runs of the reference loop on slices of pose, observation and noise.
+    ``fault``: one of MOTION_DENOISE_FAULTS, seeded on purpose.
+
+    ``details=True`` returns a dict instead: pose [T, D] (final, before smoothing), pose_steps [steps, T, D] (after every step), grad_steps
+    [steps, T, D] (the total gradient handed to Adam), adam_m / adam_v (after the last step), log [steps, S, 3] (temp, data, prior:
+    unweighted, data = 0 where the guard dropped it, prior = the sequence's own term), data_kept [steps, S] and the three metrics [T]
+    (after the Gaussian smoothing, per sequence)."""
+    assert fault is None or fault in MOTION_DENOISE_FAULTS, fault
+    legacy = dtype is None
+    if legacy:
+        dtype = torch.float32
+    else:
+        body_dtype = dtype
     T = init_poses.shape[0]
-    mean = torch.as_tensor(mean, dtype=torch.float32)
-    std = torch.as_tensor(std, dtype=torch.float32)
+    F = int(frames_per_sequence) if frames_per_sequence else T
+    S = T // F
+    assert S * F == T and F >= 2
+    seqs = [slice(s * F, (s + 1) * F) for s in range(S)]
+    if norm_mode is None:
+        norm_mode = "none"
+    if fault == "weighted_on":
+        weighted = True
+    pd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in p.items()}
+    fw = {} if embedding_type == "positional" else {"embedding_type": embedding_type}
+    mean = None if norm_mode == "none" else torch.as_tensor(mean, dtype=dtype)
+    std = None if norm_mode == "none" else torch.as_tensor(std, dtype=dtype)
     joints = torch.as_tensor(joints3d, dtype=body_dtype)
-    bm = lambda pose: fk_torch.smplx_forward(asset, pose.to(body_dtype), dtype=body_dtype)
+    asset = {k: torch.as_tensor(v, dtype=body_dtype) if isinstance(v, np.ndarray) and v.dtype.kind == "f" else v for k, v in asset.items()}
+    shape = None if betas is None else torch.as_tensor(betas, dtype=body_dtype).expand(T, -1)
+    bm = lambda pose: fk_torch.smplx_forward(asset, pose.to(body_dtype), betas=shape, dtype=body_dtype)
     with torch.no_grad():
-        v_gt, j_gt = bm(torch.as_tensor(gt_poses, dtype=torch.float32))
-    je = joints - j_gt[:, :22]
+        v_gt, j_gt = bm(torch.as_tensor(gt_poses, dtype=dtype))
+    je = joints - j_gt[:, :n_obs_joints]
     init_mpjpe = torch.mean(torch.sqrt(torch.sum(je * je, dim=2)), dim=1) * 100.0
-    pose = torch.as_tensor(init_poses, dtype=torch.float32).clone().requires_grad_(True)
+    pose = torch.as_tensor(init_poses, dtype=dtype).clone().requires_grad_(True)
     opt = torch.optim.Adam([pose], 0.03, betas=(0.9, 0.999))
     ts = torch.linspace(1.0, 1e-3, sde.N)
     total = iterations * steps_per_iter
+    z_all = torch.as_tensor(noise, dtype=dtype)
+    mmf = 1.0 if fault == "min_max_without_2" else 2.0
+    log = torch.zeros(total, S, 3, dtype=body_dtype)
+    kept = np.zeros((total, S), dtype=bool)
+    pose_steps, grad_steps = [], []
     for it in range(iterations):
         for i in range(steps_per_iter):
             step = it * steps_per_iter + i
             opt.zero_grad()
-            q = quan_t_strategy3(step, total, sde.N, sample_trun)
-            x0 = ((pose - mean) / std).detach()                                    # offline_normalize(from_axis=True), z-score
+            q = int(sample_time) if time_strategy == "2" else quan_t_strategy3(step, total, sde.N, sample_trun)
+            if not legacy:
+                _smplify_check_label(sde, float(ts[q]))
+            vec_t = torch.full((F,), float(ts[q]), dtype=dtype)
+            z = z_all[min(step + 1, total - 1) if fault == "noise_row_shifted" else step]
+            # offline_normalize(from_axis=True): z-score / min-max / none, after the 6-D conversion under rot6d
+            x_n = smplify_normalize(pose, rot6d, norm_mode, mean, std, linear_rot6d_grad=fault == "rot6d_grad_not_through_rodrigues",
+                                    min_max_factor=mmf)
+            x0 = x_n.detach()
             # DPoser_loss(x_0, vec_t, quan_t, weighted=False) (:124, called :250): unweighted here -- unlike completion.py:196,
             # whose loss() has no quan_t parameter, so quan_t lands in `weighted` there
-            _, gprior = R.dposer_prior_loss(p, sde, x0, torch.ones(T) * ts[q], torch.as_tensor(noise[step]), weighted=False,
-                                            reduction="sum_over_batch", batch_size=T)
+            gprior = torch.zeros_like(x0)
+            for s, sl in enumerate(seqs):
+                l_prior, gprior[sl] = R.dposer_prior_loss(pd, sde, x0[sl], vec_t, z[sl], weighted=weighted, reduction="sum_over_batch",
+                                                          batch_size=F, **fw)
+                log[step, s, 2] = l_prior
             v, j = bm(pose)
-            temp = v[:-1] - v[1:]
-            l_temp = torch.mean(torch.sqrt(torch.sum(temp * temp, dim=2)))
-            data = j[:, :22] - joints
-            l_data = torch.mean(torch.sqrt(torch.sum(data * data, dim=2)))
-            tot = 10.0 * l_temp * (1 + it)                                         # weights :157-163
-            if bool(l_data > 0):                                                   # :261-263
-                tot = tot + 100.0 * l_data / (1 + it * it)
+            itw = max(it - 1, 0) if fault == "prior_weight_of_previous_iteration" else it
+            w_prior = 0.1 * (1 + itw) * dposer_weight                              # weights :157-163
+            tots = []
+            for s, sl in enumerate(seqs):
+                if fault == "temporal_crosses_sequences" and s + 1 < S:
+                    vs = v[sl.start:sl.stop + 1]
+                    temp = vs[:-1] - vs[1:]
+                    l_temp = torch.sum(torch.sqrt(torch.sum(temp * temp, dim=2))) / ((F - 1) * v.shape[1])
+                else:
+                    temp = v[sl][:-1] - v[sl][1:]
+                    l_temp = torch.mean(torch.sqrt(torch.sum(temp * temp, dim=2)))
+                    if fault == "temporal_mean_over_T":
+                        l_temp = l_temp * (F - 1) / F
+                data = j[sl, :n_obs_joints] - joints[sl]
+                l_data = torch.mean(torch.sqrt(torch.sum(data * data, dim=2)))
+                if fault == "data_mean_over_frames":
+                    l_data = l_data * n_obs_joints
+                tot = 10.0 * l_temp * (1 + it)
+                keep = bool(l_data > 0) or fault == "data_guard_ignored"
+                if keep:                                                           # :261-263
+                    tot = tot + 100.0 * l_data / (1 + it * it)
+                kept[step, s] = keep
+                log[step, s, 0], log[step, s, 1] = l_temp.detach(), l_data.detach() if keep else 0.0
+                tots.append(tot)
+            tot = tots[0] if S == 1 else torch.stack(tots).sum()
+            if rot6d:
+                # x0_hat is detached (:102-104), so the prior reaches the pose through its analytic gradient and the conversion's autograd
+                x_g = x_n if fault != "prior_grad_not_divided_by_std" else smplify_normalize(pose, True, "none", None, None)
+                tot = tot + w_prior * (gprior.to(body_dtype) * x_g.to(body_dtype)).sum()
             tot.backward()
-            pose.grad += (0.1 * (1 + it) * dposer_weight) * (gprior / std)
+            if not rot6d:
+                if norm_mode == "none" or fault == "prior_grad_not_divided_by_std":
+                    gp = gprior
+                elif norm_mode == "zscore":
+                    gp = gprior / std
+                else:
+                    gp = mmf * gprior / (std - mean)
+                pose.grad += w_prior * gp
+            grad_steps.append(pose.grad.detach().clone())
             opt.step()
+            pose_steps.append(pose.detach().clone())
     final = pose.detach()
-    smooth = gaussian_smoothing(final, 3, 2.0)
-    smooth[[0, -1]] = final[[0, -1]]
+    smooth = final.clone()
+    for sl in seqs:
+        smooth[sl] = gaussian_smoothing(final[sl], 3, 2.0)
+        smooth[[sl.start, sl.stop - 1]] = final[[sl.start, sl.stop - 1]]
     with torch.no_grad():
         v, j = bm(smooth)
     je = j[:, :22] - j_gt[:, :22]
     ve = v - v_gt
     res = {"init_MPJPE": init_mpjpe.numpy(), "MPJPE": (torch.mean(torch.sqrt(torch.sum(je * je, dim=2)), dim=1) * 100.0).numpy(),
            "MPVPE": (torch.mean(torch.sqrt(torch.sum(ve * ve, dim=2)), dim=1) * 100.0).numpy()}
-    return final.numpy(), res
+    if not details:
+        return final.numpy(), res
+    state = opt.state[pose]
+    return dict(res, pose=final.numpy(), pose_steps=torch.stack(pose_steps).numpy(), grad_steps=torch.stack(grad_steps).numpy(),
+                adam_m=state["exp_avg"].numpy(), adam_v=state["exp_avg_sq"].numpy(), log=log.numpy(), data_kept=kept)
 
 
 # --------------------------------------------------------------------------------------------
