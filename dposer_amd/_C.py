@@ -17,6 +17,8 @@ EMB_POSITIONAL, EMB_FOURIER = 0, 1
 ACTIVATIONS = {"swish": 0, "elu": 1, "relu": 2, "lrelu": 3}      # config.model.nonlinearity -> DPOSER_ACT_*
 SDE_SUBVP, SDE_VP, SDE_VE, SDE_VE_DISCRETE, SDE_VP_DISCRETE = 0, 1, 2, 3, 4
 WS_INFER, WS_SHARED_T, WS_TRAIN = 0, 1, 2
+PC_PRED_NONE, PC_PRED_EULER_MARUYAMA, PC_PRED_REVERSE_DIFFUSION, PC_PRED_ANCESTRAL = 0, 1, 2, 3
+PC_CORR_NONE, PC_CORR_LANGEVIN, PC_CORR_ALD = 0, 1, 2
 
 
 class ScoreFCDesc(C.Structure):
@@ -34,6 +36,12 @@ class MlpDesc(C.Structure):
 class SdeDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("N", C.c_int32), ("beta_min", C.c_double),
                 ("beta_max", C.c_double), ("T", C.c_double)]
+
+
+class PcDesc(C.Structure):
+    """dposer_pc_desc: predictor / corrector of dposer_pc_sampler."""
+    _fields_ = [("predictor", C.c_int32), ("corrector", C.c_int32), ("n_steps_each", C.c_int32), ("probability_flow", C.c_int32),
+                ("snr", C.c_float), ("inv_global_batch", C.c_double)]
 
 
 class BodyDesc(C.Structure):
@@ -185,6 +193,8 @@ SIGNATURES = {
                                     vp, vp, i64, vp]),
     "dposer_em_sampler_steps": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, i32, i32, vp, vp, vp, u64, vp, i32,
                                           vp, vp, i64, vp]),
+    "dposer_pc_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), C.POINTER(PcDesc), vp, vp, vp, i32, i32, vp, vp, vp, u64, vp, i32,
+                                    vp, vp, vp, vp, i64, vp]),
     "dposer_langevin_step": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, f32, f32, f32, vp, u64, u32, vp, i32, f64, vp, vp,
                                        i64, vp]),
     "dposer_prior_loss": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, f32, i32, f32, vp, vp, vp, u64,

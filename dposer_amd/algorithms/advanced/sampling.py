@@ -10,8 +10,15 @@ network collapses into a per-step bias table, the predictor update / completion 
 re-tiling of x for the next step are fused into one elementwise kernel per step, and noise is
 drawn in-kernel (Philox).  With ``probability_flow=True`` (deterministic sampling along the
 probability-flow ODE, what run/demo.py's interpolation task decodes latents with) the same predictor
-runs as ``dposer_pf_sampler``: the drift's score term is halved and no noise is added or drawn.  Any
-other predictor/corrector combination runs the generic loop below on top of the HIP score function.
+runs as ``dposer_pf_sampler``: the drift's score term is halved and no noise is added or drawn.
+
+Every other registered pair -- the ``reverse_diffusion``, ``ancestral_sampling`` and ``none`` predictors, the ``langevin`` and ``ald``
+correctors -- runs as ``dposer_pc_sampler``: again one C call for the whole loop, per step [network + corrector update] x
+n_steps_each, network + predictor update, each update one elementwise kernel that also does the completion imputation and re-tiles x
+(``fused_pc_supported`` / ``fused_pc_sample``).  The discretisations read the SDE object's own ``discrete_betas`` /
+``discrete_sigmas`` on the host; the entries of a step travel to the kernels by value.  What stays outside: Langevin under data
+parallelism (``fused_pc_langevin_sample``: three calls per step around the all-reduce of the two norm sums), and probability flow with
+a corrector, other models or SDEs: the generic loop below on top of the HIP score function.
 """
 import abc
 import ctypes as C
@@ -361,6 +368,94 @@ def fused_pc_langevin_sample(model, sde, x, timesteps, *, snr, n_steps=1, start_
     return traj, x, x_mean
 
 
+_PC_PRED_KINDS = {None: _C.PC_PRED_NONE, NonePredictor: _C.PC_PRED_NONE, EulerMaruyamaPredictor: _C.PC_PRED_EULER_MARUYAMA,
+                  ReverseDiffusionPredictor: _C.PC_PRED_REVERSE_DIFFUSION, AncestralSamplingPredictor: _C.PC_PRED_ANCESTRAL}
+_PC_CORR_KINDS = {None: _C.PC_CORR_NONE, NoneCorrector: _C.PC_CORR_NONE, LangevinCorrector: _C.PC_CORR_LANGEVIN,
+                  AnnealedLangevinDynamics: _C.PC_CORR_ALD}
+
+
+def _discrete_table(sde):
+    """The SDE object's own table that the discretisations index with ``(t * (N - 1) / T).long()``: ``discrete_betas`` (sub-VP / VP,
+    ``alphas`` is 1 - it) or ``discrete_sigmas`` (VE); None when it no longer has sde.N entries (N changed after construction)."""
+    tab = sde.discrete_sigmas if isinstance(sde, sde_lib.VESDE) else getattr(sde, "discrete_betas", None)
+    if tab is None or tab.dim() != 1 or int(tab.shape[0]) != int(sde.N):
+        return None
+    return tab.detach().to("cpu", torch.float32).contiguous()
+
+
+def _pc_reads_table(sde, pred, corr):
+    """Whether the pair indexes the SDE's discrete table: ancestral sampling, reverse diffusion over the DDPM / SMLD discretisations
+    (VP / VE), and alpha of the Langevin / ALD correctors under sub-VP / VP."""
+    ve = isinstance(sde, sde_lib.VESDE)
+    return (pred == _C.PC_PRED_ANCESTRAL or (pred == _C.PC_PRED_REVERSE_DIFFUSION and not isinstance(sde, sde_lib.subVPSDE))
+            or (corr != _C.PC_CORR_NONE and not ve))
+
+
+def fused_pc_supported(sde, model, predictor, corrector, probability_flow, continuous):
+    """What ``dposer_pc_sampler`` takes from pc_sampler: every registered predictor x corrector on a fused SDE and a ScoreModelFC, except
+    * Langevin under data parallelism (its batch means need the all-reduce between the two phases: the per-step path keeps it),
+    * probability flow with a corrector (generic loop) or with ancestral sampling (the constructor's assertion must surface),
+    * ancestral sampling on sub-VP (the constructor's NotImplementedError must surface),
+    * a pair that reads the SDE's discrete table when that table no longer has sde.N entries (N changed after construction)."""
+    from ... import distributed as ddp
+    from .model import ScoreModelFC
+    if predictor not in _PC_PRED_KINDS or corrector not in _PC_CORR_KINDS:
+        return False
+    if not isinstance(model, ScoreModelFC) or sde_lib.sde_desc(sde, continuous) is None:
+        return False
+    pred, corr = _PC_PRED_KINDS[predictor], _PC_CORR_KINDS[corrector]
+    if _pc_reads_table(sde, pred, corr) and _discrete_table(sde) is None:     # (N changed after construction: the table is the constructor's)
+        return False
+    if probability_flow and (corr != _C.PC_CORR_NONE or pred == _C.PC_PRED_ANCESTRAL):
+        return False
+    if pred == _C.PC_PRED_ANCESTRAL and not isinstance(sde, (sde_lib.VPSDE, sde_lib.VESDE)):
+        return False
+    if corr == _C.PC_CORR_LANGEVIN and ddp.dp_active():
+        return False
+    return True
+
+
+def fused_pc_sample(model, sde, x, timesteps, *, predictor, corrector, snr=0.16, n_steps=1, probability_flow=False, start_step=0,
+                    run_steps=-1, observation=None, mask=None, noise=None, seed=0, traj_stride=0, continuous=True):
+    """dposer_pc_sampler: loop indices [start_step, start_step + run_steps) (run_steps < 0: to N) of sampling.py:455-461 for any
+    registered predictor / corrector class in ONE library call.  x [B, D] initial state (consumed); returns (trajs or None, x, x_mean).
+    ``noise`` [n_run, (n_steps if a corrector) + (3 if completion else 1), B, D]: injected draws in the reference's order (corrector
+    draws, impute-after-corrector, predictor z, impute-after-predictor); a slot the algorithm does not read is present and ignored."""
+    _C.require_gpu(x, "sampler state")
+    eng = model._engine()
+    flat = model.flat_params()
+    packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
+    B, D = x.shape
+    N = int(sde.N)
+    n_run = N - start_step if (run_steps < 0 or run_steps > N - start_step) else int(run_steps)
+    x = x.contiguous().float().clone()
+    if B == 0:                      # nothing to sample: the reference's loop runs on empty tensors and returns them
+        traj = torch.empty((max(n_run, 0) // traj_stride, 0, D), dtype=torch.float32, device=x.device) if traj_stride and n_run > 0 else None
+        return traj, x, x.clone()
+    ws = eng.workspace(B, _C.WS_SHARED_T, max(n_run, 1), x.device)
+    x_mean = x.clone()
+    ts_host = timesteps.detach().to("cpu", torch.float32).contiguous()
+    traj = None
+    if traj_stride and n_run > 0:
+        traj = torch.empty((n_run // traj_stride, B, D), dtype=torch.float32, device=x.device)
+    desc = sde_lib.sde_desc(sde, continuous)
+    pc = _C.PcDesc(_PC_PRED_KINDS[predictor], _PC_CORR_KINDS[corrector], int(n_steps), int(bool(probability_flow)), float(snr), 1.0 / B)
+    table = _discrete_table(sde) if _pc_reads_table(sde, pc.predictor, pc.corrector) else None
+    if table is None and _pc_reads_table(sde, pc.predictor, pc.corrector):
+        raise ValueError("the SDE's discrete table no longer has sde.N entries: this predictor / corrector pair cannot run on it")
+    norms = torch.empty(2, dtype=torch.float32, device=x.device) if pc.corrector == _C.PC_CORR_LANGEVIN else None
+    obs = None if observation is None else observation.contiguous().float()
+    msk = None if mask is None else mask.contiguous().float()
+    nz = None if noise is None else noise.contiguous().float()
+    _C.check(eng.lib.dposer_pc_sampler(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), C.byref(pc), _C.ptr(x), _C.ptr(x_mean),
+                                       C.c_void_p(ts_host.data_ptr()), int(start_step), int(run_steps), _C.ptr(obs), _C.ptr(msk), _C.ptr(nz),
+                                       int(seed), _C.ptr(traj), int(traj_stride or 1),
+                                       C.c_void_p(table.data_ptr()) if table is not None else None, _C.ptr(norms),
+                                       _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B, _C.stream_ptr()),
+             "dposer_pc_sampler")
+    return traj, x, x_mean
+
+
 def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_steps=1, probability_flow=False,
                    continuous=False, denoise=True, eps=1e-3, device="cuda"):
     """Predictor-corrector sampler factory (sampling.py:375-468).
@@ -409,6 +504,21 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                                                    mask=mask if completion else None, noise=noise, seed=seed,
                                                    traj_stride=traj_stride, continuous=continuous,
                                                    probability_flow=probability_flow)
+                model.train(was_training)
+                if trajs is None:
+                    trajs = x.new_empty((0,) + tuple(x.shape))
+                return trajs, (x_mean if denoise else x)
+            if fused_pc_supported(sde, model, predictor, corrector, probability_flow, continuous):
+                call_count[0] += 1
+                if seed is None:
+                    seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
+                was_training = model.training
+                model.eval()
+                trajs, x, x_mean = fused_pc_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), predictor=predictor,
+                                                   corrector=corrector, snr=snr, n_steps=n_steps, probability_flow=probability_flow,
+                                                   start_step=start_t, observation=observation if completion else None,
+                                                   mask=mask if completion else None, noise=noise, seed=seed,
+                                                   traj_stride=traj_stride, continuous=continuous)
                 model.train(was_training)
                 if trajs is None:
                     trajs = x.new_empty((0,) + tuple(x.shape))

@@ -757,6 +757,126 @@ hipError_t launch_langevin_update(const LangevinArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL(k_langevin_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
     return hipGetLastError();
 }
+// ---- predictors other than Euler-Maruyama (sampling.py:210-270) + imputation (:416-420): k_em_update's shape -----------------
+// The predictor kind and the SDE kind are uniform per launch (kernel arguments): the branches in pc_pred_step do not diverge.
+struct PcPredDev {
+    PcPredArgs a;
+    SdeDev sde;
+};
+template <typename T> __global__ void __launch_bounds__(256) k_pc_pred_update(PcPredDev d) {
+    const PcPredArgs& a = d.a;
+    const int qx = a.Dpad >> 2;
+    const int QD = (a.D + 3) >> 2;
+    const int64_t total = a.Bpad * qx;
+    const SdeAt at = sde_at(d.sde, a.t);
+    const float mc = at.mc, sd = at.sd;
+    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const PcPredScal ks = pc_pred_scalars(d.sde, at, a.tab, a.pred);
+    const bool score_read = a.pred != DPOSER_PC_PRED_NONE;
+    const bool draws = score_read && !a.pf;
+    float mcn = 0.f, sdn = 0.f;
+    if (a.t_next >= 0.f) { const SdeAt an = sde_at(d.sde, a.t_next); mcn = an.mc; sdn = an.sd; }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qx;              // quad index fastest: row-major [B][D] streams are read/written contiguously
+        const int q = (int)(i % qx);
+        const int c = q * 4;
+        f32x4 xn = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+            float zp[4] = {0.f, 0.f, 0.f, 0.f}, zb[4], za[4];
+            if (draws && !a.z_pred) normals4((uint64_t)s * QD + q, STREAM_EM_NOISE, a.step, a.seed, zp);
+            if (a.obs && !a.z_impB) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_B, a.step, a.seed, zb);
+            if (a.obs && a.t_next >= 0.f && !a.z_impA) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_A, a.step + 1, a.seed, za);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const int64_t o = s * a.D + c + r;
+                float x = a.x[o];
+                float score = 0.f;
+                if (score_read) score = sde_score(d.sde, a.res[s * a.Cp + c + r] / usig, at.sd_score);   // model.py:194, utils.py:162
+                const float z = (draws && a.z_pred) ? a.z_pred[o] : zp[r];
+                float x_mean;
+                x = pc_pred_step(d.sde, a.tab, ks, a.pred, a.pf, x, score, z, &x_mean);
+                a.x_mean[o] = x_mean;
+                if (a.obs) {                                                   // sampling.py:416-420 (after predictor)
+                    const float m = a.mask[o];
+                    const float nz = a.z_impB ? a.z_impB[o] : zb[r];
+                    x = x * (1.0f - m) + (mc * a.obs[o] + nz * sd) * m;
+                }
+                if (a.traj) a.traj[o] = x;                                     // sampling.py:461
+                if (a.obs && a.t_next >= 0.f) {                                // corrector 'none': imputation ahead of the next predictor call
+                    const float m = a.mask[o];
+                    const float nz = a.z_impA ? a.z_impA[o] : za[r];
+                    x = x * (1.0f - m) + (mcn * a.obs[o] + nz * sdn) * m;
+                }
+                a.x[o] = x;
+                xn[r] = x;
+            }
+        }
+        store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
+    }
+}
+hipError_t launch_pc_pred_update(const PcPredArgs& a, hipStream_t st) {
+    PcPredDev d;
+    d.a = a;
+    d.sde = make_sde_dev_at(a.sde, a.t);
+    const int64_t total = a.Bpad * (a.Dpad >> 2);
+    if (a.f32) hipLaunchKernelGGL(k_pc_pred_update<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(k_pc_pred_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+// ---- annealed Langevin dynamics (sampling.py:319-339): no batch coupling, one pass; k_langevin_update's shape -------------------
+struct AldDev {
+    AldArgs a;
+    SdeDev sde;
+};
+template <typename T> __global__ void __launch_bounds__(256) k_ald_update(AldDev d) {
+    const AldArgs& a = d.a;
+    const int qx = a.Dpad >> 2;
+    const int QD = (a.D + 3) >> 2;
+    const SdeAt at = sde_at(d.sde, a.t);
+    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float step = pc_ald_step_size(a.snr, at.sd, a.alpha);      // std of marginal_prob (:330), not the score's
+    const float nscale = sqrtf(step * 2.0f);                          // :337
+    const int64_t total = a.Bpad * qx;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qx;
+        const int q = (int)(i % qx);
+        const int c = q * 4;
+        f32x4 xn = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+            float z[4], zi[4];
+            if (!a.noise) normals4((uint64_t)s * QD + q, STREAM_LANGEVIN, a.step, a.seed, z);
+            if (a.obs && !a.z_imp) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_A, a.imp_step, a.seed, zi);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const int64_t o = s * a.D + c + r;
+                const float g = sde_score(d.sde, a.res[s * a.Cp + c + r] / usig, at.sd_score);
+                const float n = a.noise ? a.noise[o] : z[r];
+                const float xm = a.x[o] + step * g;                   // :336
+                float x = xm + n * nscale;                            // :337
+                if (a.x_mean) a.x_mean[o] = xm;
+                if (a.obs) {                                          // sampling.py:416-420 (after corrector)
+                    const float m = a.mask[o];
+                    const float nz = a.z_imp ? a.z_imp[o] : zi[r];
+                    x = x * (1.0f - m) + (at.mc * a.obs[o] + nz * at.sd) * m;
+                }
+                a.x[o] = x;
+                xn[r] = x;
+            }
+        }
+        store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
+    }
+}
+hipError_t launch_ald_update(const AldArgs& a, hipStream_t st) {
+    AldDev d;
+    d.a = a;
+    d.sde = make_sde_dev_at(a.sde, a.t);
+    const int64_t total = a.Bpad * (a.Dpad >> 2);
+    if (a.f32) hipLaunchKernelGGL(k_ald_update<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(k_ald_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
 // row-major [B][D] fp32 -> FT [Bpad][Dpad] network input (zero padded)
 template <typename T> __global__ void __launch_bounds__(256) k_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, int D, int Dpad) {
     const int qx = Dpad >> 2;

@@ -219,6 +219,49 @@ hipError_t launch_sum_partials2(const float* part, int n, float* out2, hipStream
 hipError_t launch_langevin_update(const LangevinArgs& a, hipStream_t st);
 hipError_t launch_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, int D, int Dpad, int f32, hipStream_t st);
 
+// ---- one-call predictor-corrector sampler: the predictors that are not Euler-Maruyama, and annealed Langevin dynamics ----
+struct PcPredArgs {        // ReverseDiffusion / AncestralSampling / None predictor + imputation (sampling.py:210-270, 416-420)
+    const float* res;      // [Bpad][Cp] post_dense output at x (not read by the 'none' predictor; may be null then)
+    float* x;              // [B][D] state, updated in place
+    float* x_mean;         // [B][D]
+    void* xin;             // FT [Bpad][Dpad]: the next network input
+    float* traj;           // [B][D] slot of this step or null
+    const float* sigmas;
+    const float* obs;      // completion: observation [B][D] or null
+    const float* mask;
+    const float* z_pred;   // injected predictor noise or null (-> Philox STREAM_EM_NOISE); not read under pf / by 'none'
+    const float* z_impB;   // injected imputation noise after the predictor, or null
+    const float* z_impA;   // injected imputation noise ahead of the NEXT step (corrector 'none' only), or null
+    float t, t_next;       // t_next < 0: no look-ahead imputation
+    int64_t B, Bpad;
+    int D, Dpad, Cp, num_scales, f32, scale_by_sigma;
+    SdeCfg sde;
+    PcTab tab;             // this step's table entries, by value
+    uint64_t seed;
+    uint32_t step;
+    int pred;              // DPOSER_PC_PRED_REVERSE_DIFFUSION / _ANCESTRAL / _NONE
+    int pf;
+};
+hipError_t launch_pc_pred_update(const PcPredArgs& a, hipStream_t st);
+struct AldArgs {           // AnnealedLangevinDynamics.update_fn (sampling.py:319-339), one inner step at a shared t
+    const float* res;      // [Bpad][Cp] model output at x
+    const float* noise;    // injected noise [B][D] or null (-> Philox STREAM_LANGEVIN at `step`)
+    const float* sigmas;
+    float* x;              // [B][D] in/out
+    float* x_mean;         // [B][D] out, or null: not stored (a predictor update that follows overwrites it)
+    void* xin;             // FT [Bpad][Dpad]: the new state as the next network input
+    const float* obs;      // last inner step of a completion: imputation after the corrector (sampling.py:416-420), else null
+    const float* mask;
+    const float* z_imp;    // its injected draw or null (-> Philox STREAM_IMPUTE_A at `imp_step`)
+    float t, alpha, snr;
+    int64_t B, Bpad;
+    int D, Dpad, Cp, num_scales, scale_by_sigma, f32;
+    SdeCfg sde;
+    uint64_t seed;
+    uint32_t step, imp_step;
+};
+hipError_t launch_ald_update(const AldArgs& a, hipStream_t st);
+
 struct DsmArgs {           // get_sde_loss_fn tail (losses.py:121-131) + d loss / d res
     const float* res;      // [Bpad][Cp]
     const float* t;        // [Bpad]

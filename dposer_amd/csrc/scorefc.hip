@@ -1090,6 +1090,136 @@ extern "C" int dposer_langevin_step(dposer_scorefc_t h, const float* flat, const
     return DPOSER_OK;
 }
 
+// get_pc_sampler.pc_sampler (sampling.py:429-466) for every registered predictor / corrector: include/dposer_hip.h has the contract.
+// Per loop index: [network + corrector update] x n_steps_each, [imputation], network + predictor update -- every update kernel leaves
+// the new state FT-tiled in w.xin for the next evaluation.  Euler-Maruyama goes through k_em_update and Langevin through its three
+// kernels unchanged; (Euler-Maruyama, none) IS em_sampler_impl.
+extern "C" int dposer_pc_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                 const dposer_pc_desc* pc, float* x, float* x_mean, const float* timesteps_host, int32_t start_step,
+                                 int32_t n_steps, const float* observation, const float* mask, const float* noise, uint64_t seed,
+                                 float* traj, int32_t traj_stride, const float* disc_table_host, float* norm_sums, const float* freq,
+                                 const float* sigmas, int64_t B, void* stream) {
+    DP_CHECK_ARG(pc, "null argument");
+    const int pred = pc->predictor, corr = pc->corrector, pf = pc->probability_flow ? 1 : 0;
+    DP_CHECK_ARG(pred == DPOSER_PC_PRED_NONE || pred == DPOSER_PC_PRED_EULER_MARUYAMA || pred == DPOSER_PC_PRED_REVERSE_DIFFUSION || pred == DPOSER_PC_PRED_ANCESTRAL, "unknown predictor kind");
+    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || corr == DPOSER_PC_CORR_LANGEVIN || corr == DPOSER_PC_CORR_ALD, "unknown corrector kind");
+    if (pred == DPOSER_PC_PRED_EULER_MARUYAMA && corr == DPOSER_PC_CORR_NONE)
+        return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed, traj,
+                               traj_stride, freq, sigmas, B, stream, pf);
+    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
+    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
+    DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
+    DP_CHECK_ARG((observation == nullptr) == (mask == nullptr), "observation and mask go together");
+    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
+    const SdeCfg sc = to_sde(sde);
+    if (pred == DPOSER_PC_PRED_ANCESTRAL) {      // AncestralSamplingPredictor.__init__, sampling.py:227-231
+        if (sc.kind == SDE_SUBVP) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "ancestral sampling supports the VE and VP SDEs only");
+        if (pf) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "probability flow is not supported by ancestral sampling");
+    }
+    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || pc->n_steps_each >= 1, "n_steps_each must be >= 1 with a corrector");
+    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || norm_sums, "norm_sums is required by the Langevin corrector");
+    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || pc->inv_global_batch > 0.0, "inv_global_batch must be > 0 for the Langevin corrector");
+    const bool pred_table = pred == DPOSER_PC_PRED_ANCESTRAL || (pred == DPOSER_PC_PRED_REVERSE_DIFFUSION && sc.kind != SDE_SUBVP);
+    const bool corr_table = corr != DPOSER_PC_CORR_NONE && sc.kind != SDE_VE;
+    DP_CHECK_ARG(!(pred_table || corr_table) || disc_table_host, "disc_table_host is required: the predictor or corrector reads the SDE's discrete table");
+    DpRange _dp_range("dposer_pc_sampler");          // (every argument check is above: a refused call opens no range and launches nothing)
+    g_alg_batch = B;
+    hipStream_t st = (hipStream_t)stream;
+    const char* packed = (const char*)packed_;
+    const int N = sde->N;
+    const int n_run = (n_steps < 0 || n_steps > N - start_step) ? N - start_step : n_steps;
+    if (n_run == 0) return DPOSER_OK;
+    Ws w;
+    layout_ws(h, B, DPOSER_WS_SHARED_T, n_run, (char*)ws_, w);
+    DP_TRY(stage_step_labels(h, w, sde, timesteps_host + start_step, n_run, st));
+    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_run, freq, st));
+
+    const int nc = corr == DPOSER_PC_CORR_NONE ? 0 : pc->n_steps_each;
+    const int k_noise = nc + (observation ? 3 : 1);
+    const int64_t BD = B * h->D;
+    EmUpdateArgs ea;                              // Euler-Maruyama predictor, and the stand-alone "imputation + pack" launch
+    std::memset(&ea, 0, sizeof(ea));
+    ea.x = x; ea.x_mean = x_mean; ea.xin = w.xin; ea.sigmas = sigmas; ea.obs = observation; ea.mask = mask;
+    ea.B = B; ea.Bpad = w.Bpad; ea.D = h->D; ea.Dpad = h->Dpad; ea.Cp = h->Cp; ea.num_scales = h->d.num_scales;
+    ea.f32 = h->f32; ea.scale_by_sigma = sbs_mode(h); ea.sde = sc; ea.seed = seed; ea.pf = pf;
+    PcPredArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.x = x; pa.x_mean = x_mean; pa.xin = w.xin; pa.sigmas = sigmas; pa.obs = observation; pa.mask = mask;
+    pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad; pa.Cp = h->Cp; pa.num_scales = h->d.num_scales;
+    pa.f32 = h->f32; pa.scale_by_sigma = sbs_mode(h); pa.sde = sc; pa.seed = seed; pa.pf = pf;
+    pa.pred = pred;
+    LangevinArgs la;
+    std::memset(&la, 0, sizeof(la));
+    la.res = w.res; la.sigmas = sigmas; la.x = x; la.x_mean = x_mean; la.xin = w.xin; la.part = w.loss_part; la.norm_sums = norm_sums;
+    la.snr = pc->snr; la.inv_global_batch = (float)pc->inv_global_batch; la.B = B; la.Bpad = w.Bpad; la.D = h->D; la.Dpad = h->Dpad;
+    la.Cp = h->Cp; la.num_scales = h->d.num_scales; la.scale_by_sigma = sbs_mode(h); la.f32 = h->f32; la.sde = sc; la.seed = seed;
+    AldArgs aa;
+    std::memset(&aa, 0, sizeof(aa));
+    aa.res = w.res; aa.sigmas = sigmas; aa.x = x; aa.x_mean = nullptr; aa.xin = w.xin;      // (x_mean: the predictor update that always follows writes it)
+    aa.snr = pc->snr; aa.B = B; aa.Bpad = w.Bpad;
+    aa.D = h->D; aa.Dpad = h->Dpad; aa.Cp = h->Cp; aa.num_scales = h->d.num_scales; aa.scale_by_sigma = sbs_mode(h); aa.f32 = h->f32;
+    aa.sde = sc; aa.seed = seed;
+
+    if (corr == DPOSER_PC_CORR_NONE) {
+        // step "-1": imputation ahead of the first predictor call (sampling.py:459) + pack x, as dposer_em_sampler does it
+        ea.res = nullptr; ea.t = timesteps_host[start_step]; ea.t_next = timesteps_host[start_step];
+        ea.step = (uint32_t)(start_step - 1);
+        ea.z_impA = (noise && observation) ? noise : nullptr;
+        DP_HIP_LAUNCH(launch_em_update(ea, st));
+    } else {
+        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+    }
+    for (int i = 0; i < n_run; ++i) {
+        const int gi = start_step + i;
+        const float t = timesteps_host[gi];
+        const float* nz = noise ? noise + (int64_t)i * k_noise * BD : nullptr;
+        const PcTab tab = make_pc_tab(sc, disc_table_host, t);
+        const float alpha = (corr_table) ? 1.0f - tab.tab : 1.0f;                 // sampling.py:287-291: sde.alphas = 1 - discrete_betas, fp32
+        for (int k = 0; k < nc; ++k) {
+            DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+            const float* zc = nz ? nz + (int64_t)k * BD : nullptr;
+            const uint32_t cstep = (uint32_t)((int64_t)gi * nc + k);
+            if (corr == DPOSER_PC_CORR_LANGEVIN) {
+                la.t = t; la.alpha = alpha; la.noise = zc; la.step = cstep;
+                int nb = 0;
+                DP_HIP_LAUNCH(launch_langevin_norms(la, &nb, st));
+                DP_HIP_LAUNCH(launch_sum_partials2(w.loss_part, nb, norm_sums, st));
+                DP_HIP_LAUNCH(launch_langevin_update(la, st));
+            } else {
+                const bool last = k + 1 == nc;
+                aa.t = t; aa.alpha = alpha; aa.noise = zc; aa.step = cstep; aa.imp_step = (uint32_t)gi;
+                aa.obs = last ? observation : nullptr; aa.mask = last ? mask : nullptr;
+                aa.z_imp = (last && nz && observation) ? nz + (int64_t)nc * BD : nullptr;
+                DP_HIP_LAUNCH(launch_ald_update(aa, st));
+            }
+        }
+        if (corr == DPOSER_PC_CORR_LANGEVIN && observation) {                     // imputation after the corrector + pack
+            ea.res = nullptr; ea.t = t; ea.t_next = t; ea.step = (uint32_t)(gi - 1);
+            ea.z_pred = ea.z_impB = nullptr; ea.traj = nullptr;
+            ea.z_impA = nz ? nz + (int64_t)nc * BD : nullptr;
+            DP_HIP_LAUNCH(launch_em_update(ea, st));
+        }
+        const bool ahead = corr == DPOSER_PC_CORR_NONE && i + 1 < n_run;          // look-ahead imputation fused into this update
+        const float* z_pred = nz ? nz + (int64_t)(nc + (observation ? 1 : 0)) * BD : nullptr;
+        const float* z_impB = (nz && observation) ? nz + (int64_t)(nc + 2) * BD : nullptr;
+        const float* z_impA = (nz && observation && ahead) ? nz + (int64_t)k_noise * BD : nullptr;
+        float* slot = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
+        if (pred == DPOSER_PC_PRED_EULER_MARUYAMA) {
+            DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+            ea.res = w.res; ea.t = t; ea.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; ea.step = (uint32_t)gi;
+            ea.z_pred = z_pred; ea.z_impB = z_impB; ea.z_impA = z_impA; ea.traj = slot;
+            DP_HIP_LAUNCH(launch_em_update(ea, st));
+        } else {
+            if (pred != DPOSER_PC_PRED_NONE) DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+            pa.res = w.res; pa.t = t; pa.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; pa.step = (uint32_t)gi; pa.tab = tab;
+            pa.z_pred = z_pred; pa.z_impB = z_impB; pa.z_impA = z_impA; pa.traj = slot;
+            DP_HIP_LAUNCH(launch_pc_pred_update(pa, st));
+        }
+    }
+    return DPOSER_OK;
+}
+
 // table_rows <= 0: the time-bias row is built for this call (one row).  table_rows > 0: row `row` of a table that
 // dposer_prior_table_build wrote into the same workspace (laid out for table_rows rows) -- the task loops build it once.
 static int prior_loss_impl(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,

@@ -142,3 +142,99 @@ __device__ __forceinline__ float used_sigma(const float* sigmas, int num_scales,
     idx = idx < 0 ? 0 : (idx >= num_scales ? num_scales - 1 : idx);
     return sigmas[idx];
 }
+
+// ------------------------------------------------------------------------------------------------
+// predictor / corrector stages of the one-call predictor-corrector sampler (reference sampling.py:210-259, 305-339 over
+// sde_lib.py:52-69, 111-117, 167-175, 279-287).  The discrete tables (`discrete_betas`, `discrete_sigmas`) are the SDE object's own,
+// read on the host; the entries of a step travel by value.  Operation order is the reference's, contraction off.
+// ------------------------------------------------------------------------------------------------
+// (predictor kinds: DPOSER_PC_PRED_* of include/dposer_hip.h, which common.h brings in)
+// `(t * (sde.N - 1) / sde.T).long()`: two rounded fp32 operations and a truncation (sde_lib.py:168, 280; sampling.py:235, 291, 322)
+static inline int sde_table_index(float t, int N, float T) {
+#pragma clang fp contract(off)
+    const float a = t * (float)(N - 1);
+    const float b = a / T;
+    int k = (int)b;
+    return k < 0 ? 0 : (k >= N ? N - 1 : k);
+}
+struct PcTab {
+    float tab;     // discrete_betas[timestep] (sub-VP / VP) or discrete_sigmas[timestep] (VE)
+    float adj;     // VE: discrete_sigmas[timestep - 1], 0 at timestep 0 (sde_lib.py:282-283, sampling.py:238-239)
+    float dtp;     // fp32(1 / N): `drift * dt` of the base discretize (sde_lib.py:66-68)
+    float sqdt;    // sqrt(torch.tensor(dt)): fp32 square root of fp32(1 / N)
+};
+static inline PcTab make_pc_tab(const SdeCfg& s, const float* table, float t) {
+    PcTab p;
+    p.tab = p.adj = 0.f;
+    p.dtp = (float)(1.0 / (double)s.N);
+    p.sqdt = sqrtf(p.dtp);
+    if (table) {
+        const int k = sde_table_index(t, s.N, s.T);
+        p.tab = table[k];
+        p.adj = (s.kind == SDE_VE && k > 0) ? table[k - 1] : 0.f;
+    }
+    return p;
+}
+// per-thread scalars of a predictor step: everything that does not depend on the element
+struct PcPredScal {
+    float c;       // RD: sqrt(alpha) (VP) / -0.5 beta(t) (sub-VP);  ancestral VP: sqrt(1 - beta)
+    float G;       // RD: rev_G's forward G;  ancestral: std of the added noise
+    float GG;      // RD: G ** 2;  ancestral VE: sigma^2 - adjacent^2;  ancestral VP: beta
+};
+__device__ __forceinline__ PcPredScal pc_pred_scalars(const SdeDev& s, const SdeAt& at, const PcTab& p, int pred) {
+#pragma clang fp contract(off)
+    PcPredScal r;
+    r.c = r.G = r.GG = 0.f;
+    if (pred == DPOSER_PC_PRED_REVERSE_DIFFUSION) {
+        if (s.kind == SDE_VP) {                          // DDPM discretize, sde_lib.py:167-175
+            const float alpha = 1.0f - p.tab;
+            r.c = sqrtf(alpha);
+            r.G = sqrtf(p.tab);
+        } else if (s.kind == SDE_VE) {                   // SMLD discretize, :279-287
+            r.G = sqrtf(p.tab * p.tab - p.adj * p.adj);
+        } else {                                         // base Euler form, :52-69
+            r.c = -0.5f * at.beta;
+            r.G = at.g * p.sqdt;
+        }
+        r.GG = r.G * r.G;
+    } else if (pred == DPOSER_PC_PRED_ANCESTRAL) {
+        if (s.kind == SDE_VE) {                          // sampling.py:233-243
+            const float s2 = p.tab * p.tab, a2 = p.adj * p.adj;
+            r.GG = s2 - a2;
+            r.G = sqrtf((a2 * r.GG) / s2);
+        } else {                                         // :245-253
+            r.c = sqrtf(1.0f - p.tab);
+            r.G = sqrtf(p.tab);
+            r.GG = p.tab;
+        }
+    }
+    return r;
+}
+// one element of a predictor step: x_mean and the new x (z is not read under probability flow / by the 'none' predictor)
+__device__ __forceinline__ float pc_pred_step(const SdeDev& s, const PcTab& p, const PcPredScal& k, int pred, int pf, float x, float score,
+                                              float z, float* x_mean) {
+#pragma clang fp contract(off)
+    if (pred == DPOSER_PC_PRED_REVERSE_DIFFUSION) {
+        float f;
+        if (s.kind == SDE_VP) f = k.c * x - x;
+        else if (s.kind == SDE_VE) f = 0.0f;
+        else f = (k.c * x) * p.dtp;
+        const float rev_f = f - k.GG * score;            // sde_lib.py:114-115: the full score term also under probability flow
+        const float xm = x - rev_f;                      // sampling.py:218
+        *x_mean = xm;
+        return pf ? xm : xm + k.G * z;                   // rev_G = 0 under probability flow (sde_lib.py:116)
+    }
+    if (pred == DPOSER_PC_PRED_ANCESTRAL) {
+        const float xm = s.kind == SDE_VE ? x + score * k.GG : (x + k.GG * score) / k.c;
+        *x_mean = xm;
+        return xm + k.G * z;
+    }
+    *x_mean = x;                                         // NonePredictor, sampling.py:262-270
+    return x;
+}
+// AnnealedLangevinDynamics (sampling.py:319-339): step = (snr * std) ** 2 * 2 * alpha, noise scale sqrt(step * 2)
+__device__ __forceinline__ float pc_ald_step_size(float snr, float std, float alpha) {
+#pragma clang fp contract(off)
+    const float a = snr * std;
+    return ((a * a) * 2.0f) * alpha;
+}

@@ -362,6 +362,42 @@ int dposer_langevin_step(dposer_scorefc_t h, const float* flat_params, const voi
                          float* norm_sums, int32_t phase, double inv_global_batch, const float* freq, const float* sigmas,
                          int64_t batch, void* stream);
 
+/* get_pc_sampler.pc_sampler -- sampling.py:429-466 for EVERY registered predictor and corrector, one call: loop indices
+ * [start_step, start_step + n_steps) of :455-461 (n_steps < 0: to N) are enqueued, nothing synchronises with the host, all memory is
+ * the caller's.  Arguments as dposer_em_sampler_steps, plus
+ *   pc               predictor (sampling.py:177-270), corrector (:273-350), corrector steps per loop index (`n_steps_each`, ignored by
+ *                    corrector NONE), probability_flow (sde_lib.py:98-117), snr, and 1 / global batch for the Langevin means (:296-297);
+ *   disc_table_host  N fp32 HOST entries: the SDE object's own `discrete_betas` (sub-VP / VP, sde_lib.py:136, 197) or
+ *                    `discrete_sigmas` (VE, :247).  Required when the predictor or corrector reads a table (REVERSE_DIFFUSION on VP /
+ *                    VE, ANCESTRAL, LANGEVIN / ALD on sub-VP / VP), else may be NULL.  alpha = 1.0f - beta; the index is
+ *                    (int)((t * (float)(N - 1)) / T), as `(t * (sde.N - 1) / sde.T).long()`;
+ *   norm_sums        DEVICE float[2], required for LANGEVIN.
+ * Per loop index i (t = timesteps_host[i]):  corrector x n_steps_each (LANGEVIN :282-302, ALD :319-339)  ->  imputation at t
+ * (:416-420, with `observation`)  ->  predictor (EULER_MARUYAMA :182-188; REVERSE_DIFFUSION :215-220 over RSDE.discretize
+ * sde_lib.py:111-117 and the SDE's discretize :52-69 / :167-175 / :279-287 -- under probability_flow the score term keeps factor 1 and
+ * only G is zeroed, as the reference has it; ANCESTRAL :233-253, VE / VP only and never with probability_flow; NONE :262-270)
+ * ->  imputation at t  ->  trajectory entry when (i - start_step + 1) % traj_stride == 0.  x_mean on return is the last predictor's.
+ * noise [n_run][(corrector != NONE ? n_steps_each : 0) + (observation ? 3 : 1)][B][D] injected draws in the reference's order
+ * (corrector draws, impute-after-corrector, predictor z, impute-after-predictor; a slot the algorithm does not read is present and
+ * ignored), or NULL -> Philox: STREAM_LANGEVIN at i * n_steps_each + k, STREAM_EM_NOISE at i, the imputation streams as dposer_em_sampler.
+ * (EULER_MARUYAMA, NONE) is dposer_em_sampler / dposer_pf_sampler, (EULER_MARUYAMA, LANGEVIN) the bits of dposer_langevin_step +
+ * dposer_em_sampler_steps.  Workspace: DPOSER_WS_SHARED_T with n_run table rows. */
+enum { DPOSER_PC_PRED_NONE = 0, DPOSER_PC_PRED_EULER_MARUYAMA = 1, DPOSER_PC_PRED_REVERSE_DIFFUSION = 2, DPOSER_PC_PRED_ANCESTRAL = 3 };
+enum { DPOSER_PC_CORR_NONE = 0, DPOSER_PC_CORR_LANGEVIN = 1, DPOSER_PC_CORR_ALD = 2 };
+typedef struct {
+    int32_t predictor;        /* DPOSER_PC_PRED_* */
+    int32_t corrector;        /* DPOSER_PC_CORR_* */
+    int32_t n_steps_each;     /* config.sampling.n_steps_each */
+    int32_t probability_flow;
+    float snr;                /* config.sampling.snr */
+    double inv_global_batch;  /* LANGEVIN: 1 / (number of samples the batch means run over) */
+} dposer_pc_desc;
+int dposer_pc_sampler(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws, const dposer_sde_desc* sde,
+                      const dposer_pc_desc* pc, float* x, float* x_mean, const float* timesteps_host, int32_t start_step,
+                      int32_t n_steps, const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
+                      int32_t traj_stride, const float* disc_table_host, float* norm_sums, const float* freq, const float* sigmas,
+                      int64_t batch, void* stream);
+
 /* DPoserComp.optimize -- run/completion.py:167-207 (loss :131-149, weights :151-155): `n_steps` Adam steps on the pose batch
  * x [B, D] (in: the initial value, i.e. the observation; out: the optimised variable -- the caller applies the final
  * observation/mask blend of :205) under  w_prior[i] * mean(w (x - x0_hat)^2) + w_data[i] * MSE(x * mask, obs * mask).
