@@ -161,6 +161,13 @@ class ComposeArgs(C.Structure):
                 ("out_fill", C.c_uint8 * 4), ("out", C.c_void_p)]
 
 
+class BatchGatherArgs(C.Structure):
+    """dposer_batch_gather_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("data", C.c_void_p), ("N", C.c_int64), ("D", C.c_int32), ("aux", C.c_void_p), ("N_aux", C.c_int64), ("D_aux", C.c_int32),
+                ("base", C.c_int64), ("B", C.c_int64), ("seed", C.c_uint64), ("epoch", C.c_uint32), ("out", C.c_void_p),
+                ("aux_out", C.c_void_p), ("indices", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -222,6 +229,7 @@ SIGNATURES = {
     "dposer_draw_skeletons_scratch_bytes": (i64, [i64, i32, i32]),
     "dposer_draw_skeletons": (C.c_int, [C.POINTER(DrawSkeletonsArgs), vp]),
     "dposer_compose_panels": (C.c_int, [C.POINTER(ComposeArgs), vp]),
+    "dposer_batch_gather": (C.c_int, [C.POINTER(BatchGatherArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),
     "dposer_dsm_loss_fwd_bwd_bucketed": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,

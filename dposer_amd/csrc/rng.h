@@ -13,6 +13,7 @@ enum : uint32_t {
     STREAM_IMPUTE_B = 5,
     STREAM_LANGEVIN = 6,
     STREAM_PRIOR = 7,
+    STREAM_FEED = 8,          // round function of the data feed's permutation (feed.hip; not mirrored in oracle/philox.py: tests/feed_ref.py)
     STREAM_DROPOUT0 = 16,
 };
 

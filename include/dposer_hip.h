@@ -1013,6 +1013,41 @@ typedef struct dposer_compose_args {
 } dposer_compose_args;
 int dposer_compose_panels(const dposer_compose_args* args, void* stream);
 
+/* Shuffled mini-batch gather -- the data feed of the training loop (run/train.py:70-93: a shuffling DataLoader with drop_last over a dataset
+ * of single poses), stateless and on the device: row r of the outputs is dataset row pi(seed, epoch, base + r), r in [0, B).
+ * Permutation rule.  pi(seed, epoch, .) is a bijection of [0, N), evaluated per row in the kernel; nothing is stored or sorted.  It is part
+ * of the ABI: the step -> rows map of a training run, and so what a resumed checkpoint trains on next, depends on it.
+ *   bits = ceil(log2 N) (0 for N = 1);  k = max(2, 2 ceil(bits / 2));  h = k / 2;  mask = 2^h - 1      (2^k < 4 N; N <= 2^62, so h <= 31)
+ *   x = p;  repeat
+ *       L = x >> h;  R = x & mask
+ *       for round = 0, 1, 2, 3:   F = philox4x32-10(counter = (R, epoch, 8, round), key = (seed & 0xffffffff, seed >> 32)) word 0, & mask
+ *                                 (L, R) = (R, L ^ F)
+ *       x = L << h | R
+ *   until x < N;  pi(seed, epoch, p) = x
+ *   (a balanced 4-round Feistel network on k bits, cycle-walked into [0, N): a bijection of [0, 2^k) restricted to the values below N, under
+ *   4 evaluations expected.  8 is the Philox stream id of the feed, distinct from every stream of the score and sampler kernels.)
+ *   data [N, D] fp32 row-major, any D >= 1 (rows are assumed 4-byte aligned only);  aux [N_aux >= N, D_aux] fp32 or NULL, gathered with the
+ *   same row index (the dataset's shapes, which the reference indexes un-subsampled with the pose index, lib/dataset/AMASS.py:56-58);
+ *   out [B, D], aux_out [B, D_aux], indices [B] int64 (the row indices themselves): each may be NULL, at least one is not; out needs data,
+ *   aux_out needs aux.  base >= 0, base + B <= N.  Offsets are 64-bit throughout (N D may pass 2^31 elements).
+ * One launch.  Allocates nothing, never synchronises the host. */
+typedef struct dposer_batch_gather_args {
+    const float* data;
+    int64_t N;
+    int32_t D;
+    const float* aux;
+    int64_t N_aux;
+    int32_t D_aux;
+    int64_t base;
+    int64_t B;
+    uint64_t seed;
+    uint32_t epoch;
+    float* out;
+    float* aux_out;
+    int64_t* indices;
+} dposer_batch_gather_args;
+int dposer_batch_gather(const dposer_batch_gather_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
