@@ -632,54 +632,31 @@ struct BodyTuning {
     bool fk_dma = true;                   // DPOSER_FK_DMA=0: joints-only body query through k_fk_joints instead of k_fk_joints_dma (A/B)
     int lbs_bwd_panel_order = 1;          // DPOSER_LBS_BWD_PANEL_ORDER=0: generic block -> tile order for the blend-gradient GEMMs (A/B)
     bool lbs_k_prefix = true;             // DPOSER_LBS_K_PREFIX=0: blend GEMMs over all padded pose-feature columns, posed or not (A/B)
-    int skin_bwd_mfma = 1;                // DPOSER_SKIN_BWD_MFMA=0: the LDS-walking one-pass kernel (k_skin_bwd_fused) instead of the one whose joint reduction runs
-                                          // on the matrix pipe (k_skin_bwd_mfma); 2 / 4 / 5: poses per workgroup of the latter (default 4; the temporal form 5 from 5120 frames)
+    int skin_bwd_mfma = 1;                // DPOSER_SKIN_BWD_MFMA=2 / 4 / 5: poses per workgroup of k_skin_bwd_mfma (default, and any other value: 4; the temporal form 5
+                                          // from 5120 frames)
     bool lbs_bwd_terms_parallel = true;   // DPOSER_LBS_BWD_TERMS_PARALLEL=0: the three product terms of the bf16 x 3 blend-gradient GEMM one after the other on the
                                           // caller's stream (A/B) instead of side by side on three streams
     bool lbs_bwd_rowcat = true;           // DPOSER_LBS_BWD_ROWCAT=0: the two blend-gradient product terms that read the high plane of d_offsets as two launches
                                           // (A/B) instead of ONE launch against the row-concatenated [posedirs high ; posedirs low] (round 6: the 258 MB plane is read once)
     int lbs_bwd_ksplit = 0;               // DPOSER_LBS_BWD_KSPLIT=n: force the split count of the 256x256 blend-gradient GEMMs (A/B; 0 = chosen by lbs_bwd_big_ksplit)
-    int64_t fk_lds_pad = 0;               // DPOSER_FK_LDS_PAD=bytes: extra (unused) dynamic LDS per workgroup of k_fk_joints_dma -- an occupancy probe (fewer resident
-                                          // waves per CU, same kernel): tools/fk_occupancy_sweep.sh, profiles/r06_fk_occupancy.md
-    bool lbs_fwd_chunk_serial = false;    // DPOSER_LBS_FWD_CHUNK_SERIAL=1: the chunks of DPOSER_LBS_FWD_CHUNK one after the other on the caller's stream (blend GEMM of chunk i,
-                                          // its skinning, chunk i + 1 ...): no overlap, but a chunk's offsets may still sit in the memory-side cache when they are read
-    int64_t lbs_fwd_chunk = 0;            // DPOSER_LBS_FWD_CHUNK=n (multiple of 256): the full forward runs blend GEMM and skinning in chunks of n poses, the
-                                          // skinning of chunk i on a side stream beside the GEMM of chunk i + 1 (0: one launch each over the whole batch)
-    void load() {
-        const char* e = getenv("DPOSER_FK_SMALL_MAX");
-        fk_small_max = e ? atoll(e) : (int64_t)8192;
-        e = getenv("DPOSER_LBS_JOINT_STREAM_MIN");
-        joint_stream_min = e ? atoll(e) : (int64_t)320;
-        e = getenv("DPOSER_LBS_BLEND");
-        blend_fp32 = e && e[0] == 'f';
-        e = getenv("DPOSER_SKIN_WAVE");
-        skin_mode = e ? atoi(e) : 3;
-        e = getenv("DPOSER_SKIN_BWD_FUSED");
-        skin_bwd_fused = !(e && e[0] == '0');
-        e = getenv("DPOSER_LBS_BWD_BIG");
-        lbs_bwd_big = !(e && e[0] == '0');
-        e = getenv("DPOSER_LBS_FWD_BIG");
-        lbs_fwd_big = !(e && e[0] == '0');
-        e = getenv("DPOSER_FK_DMA");
-        fk_dma = !(e && e[0] == '0');
-        e = getenv("DPOSER_LBS_K_PREFIX");
-        lbs_k_prefix = !(e && e[0] == '0');
-        e = getenv("DPOSER_LBS_BWD_PANEL_ORDER");
-        lbs_bwd_panel_order = (e && e[0] == '0') ? 0 : 1;
-        e = getenv("DPOSER_SKIN_BWD_MFMA");
-        skin_bwd_mfma = e ? atoi(e) : 1;
-        e = getenv("DPOSER_LBS_BWD_TERMS_PARALLEL");
-        lbs_bwd_terms_parallel = !(e && e[0] == '0');
-        e = getenv("DPOSER_LBS_BWD_ROWCAT");
-        lbs_bwd_rowcat = !(e && e[0] == '0');
-        e = getenv("DPOSER_LBS_BWD_KSPLIT");
-        lbs_bwd_ksplit = e ? atoi(e) : 0;
-        e = getenv("DPOSER_FK_LDS_PAD");
-        fk_lds_pad = e ? atoll(e) : (int64_t)0;
-        e = getenv("DPOSER_LBS_FWD_CHUNK_SERIAL");
-        lbs_fwd_chunk_serial = e && e[0] == '1';
-        e = getenv("DPOSER_LBS_FWD_CHUNK");
-        lbs_fwd_chunk = e ? atoll(e) / 256 * 256 : (int64_t)0;
+    void load() {      // the defaults above, overridden by what the environment sets
+        *this = BodyTuning{};
+        auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+        const char* e;
+        if ((e = getenv("DPOSER_FK_SMALL_MAX"))) fk_small_max = atoll(e);
+        if ((e = getenv("DPOSER_LBS_JOINT_STREAM_MIN"))) joint_stream_min = atoll(e);
+        if ((e = getenv("DPOSER_LBS_BLEND")) && e[0] == 'f') blend_fp32 = true;
+        if ((e = getenv("DPOSER_SKIN_WAVE"))) skin_mode = atoi(e);
+        if (off("DPOSER_SKIN_BWD_FUSED")) skin_bwd_fused = false;
+        if (off("DPOSER_LBS_BWD_BIG")) lbs_bwd_big = false;
+        if (off("DPOSER_LBS_FWD_BIG")) lbs_fwd_big = false;
+        if (off("DPOSER_FK_DMA")) fk_dma = false;
+        if (off("DPOSER_LBS_K_PREFIX")) lbs_k_prefix = false;
+        if (off("DPOSER_LBS_BWD_PANEL_ORDER")) lbs_bwd_panel_order = 0;
+        if ((e = getenv("DPOSER_SKIN_BWD_MFMA")) && atoi(e) > 0) skin_bwd_mfma = atoi(e);
+        if (off("DPOSER_LBS_BWD_TERMS_PARALLEL")) lbs_bwd_terms_parallel = false;
+        if (off("DPOSER_LBS_BWD_ROWCAT")) lbs_bwd_rowcat = false;
+        if ((e = getenv("DPOSER_LBS_BWD_KSPLIT"))) lbs_bwd_ksplit = atoi(e);
     }
 };
 static BodyTuning& body_tuning() {
@@ -791,18 +768,10 @@ struct dposer_body_s {
     int32_t* jl_ptr = nullptr;       // device [chunks][J + 1] entry ranges, relative to the chunk's first entry
     int32_t* jl_first = nullptr;     // device [chunks + 1] first entry of each chunk
     float2* jl_entry = nullptr;      // device [nnz] (weight, local vertex index as int bits)
-    // k_skin_bwd_fused's tables (same setup call): every chunk's joint lists cut into segments of <= 32 entries
-    bool jl_fused_ok = false;        // chunks are the regular 256-vertex grid, <= 1024 entries and <= 128 segments per chunk, K = 4
-    int32_t* jl_seg = nullptr;       // device [chunks][128] x int2 (begin, end) relative to the chunk's first entry
-    int32_t* jl_nseg = nullptr;      // device [chunks]
-    int32_t* jl_jseg = nullptr;      // device [chunks][J] (first segment | count << 16) of joint j in chunk c
     // k_skin_bwd_mfma's table (same setup call): the skinning weights of every 256-vertex chunk as a dense [64 joints][256 vertices] matrix,
     // bf16 hi / lo planes, in the lane order of the MFMA A operand (64 KB per chunk; J <= 64, regular chunks)
-    bool jl_mfma_ok = false;
     void* jl_wfrag = nullptr;
-    // chunked forward: the skinning of chunk i runs on this stream beside the blend GEMM of chunk i + 1 (created on first use)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_chunk[2] = {nullptr, nullptr}, ev_join = nullptr;
+    bool jl_onepass_ok = false;      // the one-pass backward (k_skin_bwd_mfma) may run: see dposer_lbs_prepare_joint_lists
     // backward: the three product terms of the bf16 x 3 blend-gradient GEMM run side by side on the caller's stream and these two
     hipStream_t bwd_side[2] = {nullptr, nullptr};
     hipEvent_t ev_bwd_fork = nullptr, ev_bwd_join[2] = {nullptr, nullptr};
@@ -815,10 +784,8 @@ static int side_streams_for_current_device(dposer_body_t h) {
     int dev = -1;
     DP_CHECK_HIP(hipGetDevice(&dev));
     if (h->side_dev == dev) return DPOSER_OK;
-    if (h->side) (void)hipStreamDestroy(h->side);
     for (hipStream_t* q : {&h->bwd_side[0], &h->bwd_side[1]}) { if (*q) (void)hipStreamDestroy(*q); *q = nullptr; }
-    for (hipEvent_t* e : {&h->ev_chunk[0], &h->ev_chunk[1], &h->ev_join, &h->ev_bwd_fork, &h->ev_bwd_join[0], &h->ev_bwd_join[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    h->side = nullptr;
+    for (hipEvent_t* e : {&h->ev_bwd_fork, &h->ev_bwd_join[0], &h->ev_bwd_join[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     h->side_dev = dev;
     return DPOSER_OK;
 }
@@ -850,11 +817,10 @@ extern "C" int dposer_body_create(const dposer_body_desc* desc, const int32_t* p
 extern "C" void dposer_body_destroy(dposer_body_t h) {
     if (!h) return;
     (void)hipFree(h->jl_vstart); (void)hipFree(h->jl_ptr); (void)hipFree(h->jl_first); (void)hipFree(h->jl_entry);
-    (void)hipFree(h->jl_seg); (void)hipFree(h->jl_nseg); (void)hipFree(h->jl_jseg); (void)hipFree(h->jl_wfrag);
-    if (h->side) (void)hipStreamDestroy(h->side);
+    (void)hipFree(h->jl_wfrag);
     for (hipStream_t q : {h->bwd_side[0], h->bwd_side[1]})
         if (q) (void)hipStreamDestroy(q);
-    for (hipEvent_t e : {h->ev_chunk[0], h->ev_chunk[1], h->ev_join, h->ev_bwd_fork, h->ev_bwd_join[0], h->ev_bwd_join[1]})
+    for (hipEvent_t e : {h->ev_bwd_fork, h->ev_bwd_join[0], h->ev_bwd_join[1]})
         if (e) (void)hipEventDestroy(e);
     delete h;
 }
@@ -880,7 +846,7 @@ template <typename Kin> static hipError_t launch_fk(const FkArgs& a, hipStream_t
                             (((uintptr_t)a.seg[0] | (uintptr_t)a.seg[1] | (uintptr_t)a.joints) & 15) == 0;
         if (dma_ok) {        // full blocks of 64 poses through the DMA kernel, the remaining < 64 poses through the general one
             const int64_t nfull = a.B / 64, rem = a.B - nfull * 64;
-            hipLaunchKernelGGL(k_fk_joints_dma<Kin>, dim3((unsigned)nfull), dim3(64), 64 * 66 * sizeof(float) + (size_t)body_tuning().fk_lds_pad, st, a);
+            hipLaunchKernelGGL(k_fk_joints_dma<Kin>, dim3((unsigned)nfull), dim3(64), 64 * 66 * sizeof(float), st, a);
             if (rem == 0) return hipGetLastError();
             FkArgs t = a;
             const int64_t o = nfull * 64;
@@ -1277,48 +1243,9 @@ extern "C" int64_t dposer_lbs_workspace_bytes(dposer_body_t h, int64_t batch) {
 }
 
 // FK + pose-blend GEMM of the LBS forward (steps 1 and 2); A / offsets: where the skinning stage finds its inputs in `ws`
-// The pose-blend GEMM of the padded pose rows [r0, r1) (multiples of the 256 / 128-row tile): lbs_forward_front runs it over the whole batch,
-// the chunked forward (dposer_lbs_forward) chunk by chunk with the skinning of the previous chunk running beside it.
-struct LbsBlend {
-    float* pf;
-    __bf16* pf_split;
-    float* offsets;
-    const void* posedirs_packed;
-    int Keff, Ppad, V;
-    int64_t Cpad, Bpad, batch;
-};
-static int lbs_blend_rows(const LbsBlend& b, int64_t r0, int64_t r1, hipStream_t st) {
-    GemmArgs g;
-    std::memset(&g, 0, sizeof(g));
-    WgradParams wp;
-    const int64_t valid = (b.batch < r1 ? b.batch : r1) - r0;
-    if (valid <= 0) return DPOSER_OK;
-    wp.slab = b.offsets + r0 * b.Cpad; wp.slab_stride = 0; wp.ld = (int)b.Cpad; wp.N_valid = (int)valid; wp.K_valid = b.V * 3;
-    g.ksplit = 1;
-    const int64_t rows = r1 - r0;
-    if (lbs_blend_fp32()) {
-        g.W = (const char*)b.pf + (r0 / 32) * (int64_t)(b.Ppad / 8) * 1024; g.w_stride_blocks = b.Ppad / 8; g.n_cblk = (int)(rows / 128); g.n_sblk = (int)(b.Cpad / 128);
-        g.src[0] = b.posedirs_packed; g.seg_kblocks[0] = b.Keff / 8; g.seg_stride_blocks[0] = b.Ppad / 8; g.nseg = 1; g.ktot_blocks = b.Keff / 8;
-        FK_HIP_LAUNCH(gemm_wgrad(PREC_FP32, SHAPE_MID, g, wp, st));
-    } else {
-        const char* hi = (const char*)b.posedirs_packed + b.Cpad * b.Ppad * 4;
-        const char* lo = hi + b.Cpad * b.Ppad * 2;
-        const int kb = b.Ppad / 16, kbe = b.Keff / 16;
-        const int shape = (rows % 256 == 0 && b.Cpad % 256 == 0 && b.Bpad >= 1024 && body_tuning().lbs_fwd_big) ? SHAPE_BIG : SHAPE_MID;
-        const int tile = shape == SHAPE_BIG ? 256 : 128;
-        g.W = (const char*)b.pf_split + (r0 / 32) * (int64_t)(3 * kbe) * 1024; g.w_stride_blocks = 3 * kbe; g.n_cblk = (int)(rows / tile); g.n_sblk = (int)(b.Cpad / tile);
-        g.src[0] = hi; g.src[1] = lo; g.src[2] = hi;                        // [pf_hi | pf_hi | pf_lo] x [hi ; lo ; hi]
-        g.seg_kblocks[0] = g.seg_kblocks[1] = g.seg_kblocks[2] = kbe; g.nseg = 3; g.ktot_blocks = 3 * kbe;
-        g.seg_stride_blocks[0] = g.seg_stride_blocks[1] = g.seg_stride_blocks[2] = kb;      // (rows of the packed posedirs keep their full width)
-        FK_HIP_LAUNCH(gemm_wgrad(PREC_BF16, shape, g, wp, st));
-    }
-    return DPOSER_OK;
-}
-
 static int lbs_forward_front(dposer_body_t h, void* ws, const void* posedirs_packed, const float* const* pose_segments_host,
                              const int32_t* segment_joints_host, int32_t num_segments, const float* j_rest, int32_t j_rest_batched,
-                             const float* transl, float* joints, int64_t batch, void* stream, float** A_out, float** offsets_out,
-                             LbsBlend* blend = nullptr) {
+                             const float* transl, float* joints, int64_t batch, void* stream, float** A_out, float** offsets_out) {
     DP_CHECK_ARG(h && ws && posedirs_packed && pose_segments_host && segment_joints_host && j_rest && joints, "null argument");
     DP_CHECK_ARG(batch > 0, "bad size");
     DP_CHECK_ARG(((uintptr_t)ws & 255) == 0 && ((uintptr_t)posedirs_packed & 255) == 0, "workspace / packed posedirs must be 256-byte aligned");
@@ -1360,14 +1287,26 @@ static int lbs_forward_front(dposer_body_t h, void* ws, const void* posedirs_pac
         hipLaunchKernelGGL(k_split_pf, dim3((unsigned)ceil_div(Bpad * (Keff / 8), 256)), dim3(256), 0, st, (const float*)pf, pf_split, Bpad, Ppad, Keff);
         FK_HIP_LAUNCH(hipGetLastError());
     }
-    if (blend) {
-        blend->pf = pf; blend->pf_split = pf_split; blend->offsets = offsets; blend->posedirs_packed = posedirs_packed;
-        blend->Keff = Keff; blend->Ppad = Ppad; blend->Cpad = Cpad; blend->Bpad = Bpad; blend->batch = batch; blend->V = V;
+    GemmArgs g;
+    std::memset(&g, 0, sizeof(g));
+    WgradParams wp;
+    wp.slab = offsets; wp.slab_stride = 0; wp.ld = (int)Cpad; wp.N_valid = (int)batch; wp.K_valid = V * 3;
+    g.ksplit = 1;
+    if (lbs_blend_fp32()) {
+        g.W = pf; g.w_stride_blocks = Ppad / 8; g.n_cblk = (int)(Bpad / 128); g.n_sblk = (int)(Cpad / 128);
+        g.src[0] = posedirs_packed; g.seg_kblocks[0] = Keff / 8; g.seg_stride_blocks[0] = Ppad / 8; g.nseg = 1; g.ktot_blocks = Keff / 8;
+        FK_HIP_LAUNCH(gemm_wgrad(PREC_FP32, SHAPE_MID, g, wp, st));
     } else {
-        LbsBlend b;
-        b.pf = pf; b.pf_split = pf_split; b.offsets = offsets; b.posedirs_packed = posedirs_packed;
-        b.Keff = Keff; b.Ppad = Ppad; b.Cpad = Cpad; b.Bpad = Bpad; b.batch = batch; b.V = V;
-        DP_TRY(lbs_blend_rows(b, 0, Bpad, st));
+        const char* hi = (const char*)posedirs_packed + Cpad * Ppad * 4;
+        const char* lo = hi + Cpad * Ppad * 2;
+        const int kb = Ppad / 16, kbe = Keff / 16;
+        const int shape = (Bpad % 256 == 0 && Cpad % 256 == 0 && Bpad >= 1024 && body_tuning().lbs_fwd_big) ? SHAPE_BIG : SHAPE_MID;
+        const int tile = shape == SHAPE_BIG ? 256 : 128;
+        g.W = pf_split; g.w_stride_blocks = 3 * kbe; g.n_cblk = (int)(Bpad / tile); g.n_sblk = (int)(Cpad / tile);
+        g.src[0] = hi; g.src[1] = lo; g.src[2] = hi;                        // [pf_hi | pf_hi | pf_lo] x [hi ; lo ; hi]
+        g.seg_kblocks[0] = g.seg_kblocks[1] = g.seg_kblocks[2] = kbe; g.nseg = 3; g.ktot_blocks = 3 * kbe;
+        g.seg_stride_blocks[0] = g.seg_stride_blocks[1] = g.seg_stride_blocks[2] = kb;      // (rows of the packed posedirs keep their full width)
+        FK_HIP_LAUNCH(gemm_wgrad(PREC_BF16, shape, g, wp, st));
     }
     *A_out = A;
     *offsets_out = offsets;
@@ -1387,11 +1326,8 @@ extern "C" int dposer_lbs_forward(dposer_body_t h, void* ws, const void* posedir
     const int J = h->d.num_joints, V = h->d.num_vertices;
     const int64_t Cpad = lbs_cpad(V);
     const int n_total = J + h->d.num_extra + h->d.num_landmarks;
-    const int64_t chunk = body_tuning().lbs_fwd_chunk;
-    const bool chunked = chunk >= 256 && batch > chunk;
-    LbsBlend blend;
     DP_TRY(lbs_forward_front(h, ws, posedirs_packed, pose_segments_host, segment_joints_host, num_segments, j_rest, j_rest_batched, transl, joints,
-                             batch, stream, &A, &offsets, chunked ? &blend : nullptr));
+                             batch, stream, &A, &offsets));
     // 3. skinning of the poses [b0, b0 + nb)
     auto skin = [&](int64_t b0, int64_t nb, hipStream_t ss) -> int {
         SkinArgs s;
@@ -1410,36 +1346,7 @@ extern "C" int dposer_lbs_forward(dposer_body_t h, void* ws, const void* posedir
         FK_HIP_LAUNCH(hipGetLastError());
         return DPOSER_OK;
     };
-    if (!chunked) {
-        DP_TRY(skin(0, batch, st));
-    } else {
-        // blend GEMM chunk by chunk on the caller's stream; the skinning of a finished chunk runs on the side stream beside the next
-        // chunk's GEMM (matrix pipe beside a streaming kernel), and reads its pose-blend offsets while they are still cache-resident
-        DP_TRY(side_streams_for_current_device(h));
-        if (!h->side) {
-            DP_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&h->ev_chunk[0], &h->ev_chunk[1], &h->ev_join}) DP_CHECK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-        // (a failing launch must not leave the side stream's kernels unjoined: the caller may free or reuse the workspace as soon as
-        //  this call has returned -- the join below runs on the error path too)
-        const bool serial = body_tuning().lbs_fwd_chunk_serial;
-        auto chunks = [&]() -> int {
-            int k = 0;
-            for (int64_t b0 = 0; b0 < batch; b0 += chunk, ++k) {
-                const int64_t r1 = b0 + chunk < blend.Bpad ? b0 + chunk : blend.Bpad;
-                DP_TRY(lbs_blend_rows(blend, b0, b0 + chunk >= batch ? blend.Bpad : r1, st));
-                if (serial) { DP_TRY(skin(b0, (b0 + chunk < batch ? b0 + chunk : batch) - b0, st)); continue; }
-                DP_CHECK_HIP(hipEventRecord(h->ev_chunk[k & 1], st));
-                DP_CHECK_HIP(hipStreamWaitEvent(h->side, h->ev_chunk[k & 1], 0));
-                DP_TRY(skin(b0, (b0 + chunk < batch ? b0 + chunk : batch) - b0, h->side));
-            }
-            return DPOSER_OK;
-        };
-        const int rc_chunks = chunks();
-        DP_CHECK_HIP(hipEventRecord(h->ev_join, h->side));
-        DP_CHECK_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-        if (rc_chunks != DPOSER_OK) return rc_chunks;
-    }
+    DP_TRY(skin(0, batch, st));
     // 4. extra joints + landmarks
     // (all three tables NULL: the caller reads tree joints only -- rows [J, J + num_extra + num_landmarks) of `joints` are left unwritten)
     if (h->d.num_extra + h->d.num_landmarks > 0 && (extra_vertex_ids || lmk_tri || lmk_bary)) {
@@ -1928,211 +1835,20 @@ __global__ void __launch_bounds__(128) k_skin_bwd_joints_gather(JointGatherArgs 
     }
     if (threadIdx.x < 12) a.dA[(b * a.J + j) * 12 + threadIdx.x] = red[0][threadIdx.x];
 }
-// Skinning backward in ONE streaming pass per pose (round 3): k_skin_bwd + k_skin_bwd_joints read d_verts twice and pass v_posed
-// through HBM (516 MB written and read back at 4096 SMPL-X poses; PMC: 2.8 + 1.05 GB for the pair).  One block per pose walks the
-// regular 256-vertex chunks; per chunk
-//   A  thread = vertex: T = sum_k w_k A[j_k], g = T_R^T dv, p = v_shaped + offsets  ->  LDS (dv, p, g) + the chunk's entry / segment tables
-//   B  g leaves as the two bf16 terms of the blend GEMM's operand (FT) [and as d v_posed if asked for]; the 64 lane quads take the
-//      chunk's segments (12 ... 32 list entries each, one per quad: see dposer_lbs_prepare_joint_lists) and leave partial sums in LDS
-//   C  the 4 lanes that own joint j add its segments' partials, in table order, to their running dA[j] (registers, whole pose)
-// Two barriers per chunk; the next chunk's global loads are issued before B.  Summation order: entries inside a segment in list
-// order, segments in order, chunks in order: deterministic (and different from k_skin_bwd_joints' by rounding only).
-constexpr int FUSED_MAXSEG = 128, FUSED_MAXE = 1024;
-struct SkinBwdFusedArgs {
-    VertGrad vg;
-    const float* dverts;       // [B][V][3]
-    const float* offsets;      // [B][ld_off]
-    int64_t ld_off;
-    const float* v_shaped;
-    int v_shaped_batched;
-    const float* A;            // [B][J][12]
-    const int32_t* skin_idx;   // [V][4]
-    const float* skin_w;       // [V][4]
-    int J, V;
-    float* dvp;                // [B][V][3] or null
-    __bf16* doff_hi;           // FT bf16 [Bpad][Cpad]
-    __bf16* doff_lo;
-    int Cpad;
-    const int32_t* cfirst;     // [chunks + 1]
-    const float2* entry;       // [nnz]
-    const int2* seg;           // [chunks][FUSED_MAXSEG]
-    const int32_t* nseg;       // [chunks]
-    const int32_t* jseg;       // [chunks][J]
-    float* dA;                 // [B][J][12]
-    int chunks;
-    int64_t B;
-};
-__global__ void __launch_bounds__(256) k_skin_bwd_fused(SkinBwdFusedArgs a) {
-    __shared__ __attribute__((aligned(16))) float sA[64 * 12];
-    __shared__ f32x4 sP[4 * 257];           // [q][vertex] planes of 257 records (conflict-free 16-byte writes; the quad's four reads land 4 banks apart): per vertex and q the products dv_r * [p ; 1]_q (r = 0..2, one 16-byte record): formed ONCE per vertex by
-                                            // its own thread (a vertex sits in four joint lists; per list entry a lane does one 16-byte read, 3 FMAs)
-    __shared__ float stage[768];            // g = d loss / d v_posed of the chunk, coordinate-major
-    __shared__ float2 sent[FUSED_MAXE];
-    __shared__ int2 sseg[FUSED_MAXSEG];
-    __shared__ float part[FUSED_MAXSEG][4][3];
-    // block -> pose: the FT operand keeps 4 consecutive poses in one 128-byte line (32 B each), and block i runs on XCD i % 8 with its
-    // own L2 -- blocks 32 g + 8 i + x (i < 4) take the poses 32 g + 4 x + i, so that the four writers of a line share an L2 and are
-    // dispatched back to back (the PMC counted 1043 MB written for 516 MB of operand with the identity map)
-    const int64_t blk = blockIdx.x;
-    const int64_t b = (blk < (a.B & ~(int64_t)31)) ? (blk & ~(int64_t)31) + 4 * (blk & 7) + ((blk >> 3) & 3) : blk;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < a.J * 12; i += 256) sA[i] = a.A[b * a.J * 12 + i];
-    const float* vs_row = a.v_shaped + (a.v_shaped_batched ? b * a.V * 3 : 0);
-    const float* off_row = a.offsets + b * a.ld_off;
-    const float* dv_row = a.dverts + b * a.V * 3;
-    const int jq = tid >> 2, q = tid & 3;                  // joint owner / segment worker: quad and lane inside it
-    float tot[3] = {0.f, 0.f, 0.f};
-    // the chunk's per-vertex loads (clamped: tail threads load a valid vertex and contribute zeros)
-    float dv[3], pp[3];
-    f32x4 w4;
-    int4 j4;
-    auto load_vertex = [&](int c) __attribute__((always_inline)) {
-        const int v = c * 256 + tid;
-        const int vc = v < a.V ? v : a.V - 1;
-        const float* dvr = a.vg.vslot ? a.vg.row(b, vc, a.V) : dv_row + (int64_t)vc * 3;     // (corrected row where a landmark / extra joint touches the vertex)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { dv[k] = dvr[k]; pp[k] = vs_row[(int64_t)vc * 3 + k] + off_row[(int64_t)vc * 3 + k]; }
-        w4 = *reinterpret_cast<const f32x4*>(a.skin_w + (int64_t)vc * 4);
-        j4 = *reinterpret_cast<const int4*>(a.skin_idx + (int64_t)vc * 4);
-    };
-    // ... and its tables (entries, segment bounds, this quad's joint): registers, one chunk ahead like the vertex data; the per-chunk
-    // counts sit in LDS (a dependent scalar load -> global load -> LDS chain per chunk was most of the first version's time)
-    __shared__ int scf[64], sns[64];
-    for (int i = tid; i <= a.chunks && i < 64; i += 256) scf[i] = a.cfirst[i];
-    for (int i = tid; i < a.chunks && i < 64; i += 256) sns[i] = a.nseg[i];
-    float2 en_r[4];
-    int2 sg_r;
-    int js_r;
-    auto load_tables = [&](int c) __attribute__((always_inline)) {
-        const int e0 = scf[c], ne = scf[c + 1] - e0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = tid + 256 * i;
-            en_r[i] = a.entry[e0 + (k < ne ? k : 0)];
-        }
-        sg_r = a.seg[(int64_t)c * FUSED_MAXSEG + (tid < FUSED_MAXSEG ? tid : 0)];
-        js_r = a.jseg[(int64_t)c * a.J + (jq < a.J ? jq : 0)];
-    };
-    __syncthreads();
-    load_vertex(0);
-    load_tables(0);
-    for (int c = 0; c < a.chunks; ++c) {
-        const int v0 = c * 256, v = v0 + tid;
-        const int ne = scf[c + 1] - scf[c], ns = sns[c];
-        // ---- A
-        {
-            const bool live = v < a.V;
-            const int jj[4] = {j4.x, j4.y, j4.z, j4.w};
-            float T[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) T[i] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4* Aj = reinterpret_cast<const f32x4*>(sA) + jj[k] * 3;    // 16-byte reads: see k_skin_x4
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const f32x4 row = Aj[r];
-#pragma unroll
-                    for (int cc = 0; cc < 3; ++cc) T[3 * r + cc] += w4[k] * row[cc];
-                }
-            }
-            const float dx = live ? dv[0] : 0.f, dy = live ? dv[1] : 0.f, dz = live ? dv[2] : 0.f;
-            const float hv[4] = {pp[0], pp[1], pp[2], 1.0f};
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                f32x4 o;
-                o[0] = dx * hv[qq]; o[1] = dy * hv[qq]; o[2] = dz * hv[qq]; o[3] = 0.f;
-                sP[qq * 257 + tid] = o;
-            }
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc) stage[tid * 3 + cc] = T[cc] * dx + T[3 + cc] * dy + T[6 + cc] * dz;      // T_R^T dv
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (tid + 256 * i < ne) sent[tid + 256 * i] = en_r[i];
-        if (tid < ns) sseg[tid] = sg_r;
-        const int js = (jq < a.J) ? js_r : 0;                               // this quad's joint: (first segment | count << 16)
-        if (c + 1 < a.chunks) { load_vertex(c + 1); load_tables(c + 1); }   // in flight across B and C
-        __syncthreads();
-        // ---- B: outputs of the vertex half
-        {
-            const int nval = (a.V - v0 < 256 ? a.V - v0 : 256) * 3;
-            if (a.dvp) {
-                const int64_t row = (b * a.V + v0) * 3;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int k = i * 256 + tid;
-                    if (k < nval) a.dvp[row + k] = stage[k];
-                }
-            }
-            if (tid < 96) {
-                const int k8 = v0 * 3 + tid * 8;                                     // first coordinate of this 8-element chunk
-                if (k8 < a.Cpad) {
-                    __bf16 hi[8], lo[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float x = (tid * 8 + e < nval) ? stage[tid * 8 + e] : 0.f;
-                        hi[e] = (__bf16)x;
-                        lo[e] = (__bf16)(x - (float)hi[e]);
-                    }
-                    *reinterpret_cast<u32x4*>(a.doff_hi + FT<__bf16>::index(b, k8, a.Cpad)) = *reinterpret_cast<u32x4*>(hi);
-                    *reinterpret_cast<u32x4*>(a.doff_lo + FT<__bf16>::index(b, k8, a.Cpad)) = *reinterpret_cast<u32x4*>(lo);
-                }
-            }
-        }
-        // ---- B: segments
-        for (int sgi = jq; sgi < ns; sgi += 64) {
-            const int2 se = sseg[sgi];
-            float acc[3] = {0.f, 0.f, 0.f};
-            // four entries per iteration, ONE entry read per lane: lane q of the quad fetches entry i + q, DPP quad broadcasts hand every
-            // entry to all four lanes (the LDS pipe is this kernel's bound; a per-lane read of the same entry by all four lanes costs an LDS
-            // instruction each).  Entries past the segment's end carry weight 0 and vertex 0.  Sums in list order.
-            for (int i = se.x; i < se.y; i += 4) {
-                const bool in = i + q < se.y;
-                const float2 mine = sent[in ? i + q : se.x];
-                const int wbits = in ? __float_as_int(mine.x) : 0, lbits = in ? __float_as_int(mine.y) : 0;
-                f32x4 pr[4];
-                float wu[4];
-#define DP_QUAD_BCAST(U)                                                                              \
-    wu[U] = __int_as_float(__builtin_amdgcn_mov_dpp(wbits, U * 0x55, 0xf, 0xf, false));                 \
-    pr[U] = sP[q * 257 + __builtin_amdgcn_mov_dpp(lbits, U * 0x55, 0xf, 0xf, false)]      /* quad_perm: [U, U, U, U] */
-                DP_QUAD_BCAST(0); DP_QUAD_BCAST(1); DP_QUAD_BCAST(2); DP_QUAD_BCAST(3);
-#undef DP_QUAD_BCAST
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) acc[r] += wu[u] * pr[u][r];
-            }
-#pragma unroll
-            for (int r = 0; r < 3; ++r) part[sgi][q][r] = acc[r];
-        }
-        __syncthreads();
-        // ---- C
-        {
-            const int f = js & 0xffff, n = js >> 16;
-            for (int i = 0; i < n; ++i)
-#pragma unroll
-                for (int r = 0; r < 3; ++r) tot[r] += part[f + i][q][r];
-        }
-    }
-    if (jq < a.J) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) a.dA[(b * a.J + jq) * 12 + 4 * r + q] = tot[r];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Skinning backward with the joint reduction on the MATRIX PIPE (round 5).  k_skin_bwd_fused is LDS-bound: every one of a chunk's
-// ~1024 (vertex, joint) list entries costs four 16-byte LDS reads (65 KB per pose and chunk, a third of them bank conflicts).  The
+// Skinning backward in ONE streaming pass per pose, with the joint reduction on the MATRIX PIPE (round 5).  k_skin_bwd + k_skin_bwd_joints
+// read d_verts twice and pass v_posed through HBM (516 MB written and read back at 4096 SMPL-X poses); walking a chunk's ~1024 (vertex,
+// joint) list entries in LDS instead is LDS-bound (four 16-byte reads per entry, a third of them bank conflicts: 861 us against this
+// kernel's 544 us at 4096 poses, profiles/r05_skin_bwd_ablation.txt).  The
 // reduction  dA[j][4 r + q] = sum_v W[v][j] * (dv_r [p ; 1]_q)  is a GEMM with a sparse factor -- D [64 joints][12] = W^T [64][256] P [256][12] per
 // pose and chunk -- and small enough for the dense form: 8 k-steps x 4 joint tiles of v_mfma_f32_16x16x32_bf16, three products per term
 // (bf16 hi / lo planes of both factors, fp32 accumulate: the arithmetic of the blend GEMMs).  A workgroup owns G consecutive poses and
 // walks the chunks; wave w reduces the chunk's vertices [64 w, 64 w + 64) for all 64 joints: its slice of W^T -- 16 fragments, prepared in
 // lane order by dposer_lbs_prepare_joint_lists -- is loaded from L2 once per chunk and serves the G poses from registers; P is formed
-// once per vertex by the vertex's thread (as before), leaves as 24 two-byte LDS writes and is read back ONCE (four 16-byte reads per
+// once per vertex by the vertex's thread, leaves as 24 two-byte LDS writes and is read back ONCE (four 16-byte reads per
 // lane).  The running dA of every pose stays in accumulator registers over the whole walk; the four waves' partial sums meet in LDS at
 // the end.  One barrier per pose and chunk (P and the d v_posed stage are double-buffered).  Deterministic; differs from
-// k_skin_bwd_fused by the rounding of the split products (~1e-6 relative).
+// k_skin_bwd_joints' sums by the rounding of the split products (~1e-6 relative).
 // ------------------------------------------------------------------------------------------------
 constexpr int SBM_PSTRIDE = 72;                  // bf16 per row of a wave's P plane: 64 vertices + 8 (144 B: the 16 rows of a fragment read land 4 banks apart)
 constexpr int SBM_PLANE = 16 * SBM_PSTRIDE;      // 12 product rows + 4 zero rows
@@ -2559,53 +2275,11 @@ extern "C" int dposer_lbs_prepare_joint_lists(dposer_body_t h, const int32_t* jp
     DP_CHECK_HIP(hipMemcpy(h->jl_first, cfirst.data(), cfirst.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     DP_CHECK_HIP(hipMemcpy(h->jl_entry, entry.data(), entry.size() * sizeof(float2), hipMemcpyHostToDevice));
     h->jl_chunks = chunks;
-    // segment tables of the fused backward kernel: joint j's run in chunk c cut into pieces of <= 32 entries, so that the 64 lane
-    // quads of a block share a chunk's ~1024 entries evenly (a chunk's vertices hang on a handful of joints: whole runs per quad,
-    // as k_skin_bwd_joints walks them, leave one quad with hundreds of entries and the rest idle)
-    (void)hipFree(h->jl_seg); (void)hipFree(h->jl_nseg); (void)hipFree(h->jl_jseg);
-    h->jl_seg = nullptr; h->jl_nseg = nullptr; h->jl_jseg = nullptr;
-    h->jl_fused_ok = false;
-    {
-        bool ok = true;
-        std::vector<int32_t> seg((size_t)chunks * FUSED_MAXSEG * 2, 0), nseg(chunks, 0), jseg((size_t)chunks * J, 0);
-        for (int c = 0; c < chunks && ok; ++c) {
-            if (vstart[c] != c * 256 || cfirst[c + 1] - cfirst[c] > FUSED_MAXE) { ok = false; break; }
-            const int32_t* pj = &cnt[(size_t)c * (J + 1)];
-            // shortest segment length that gives every one of the block's 64 quads at most one segment
-            int len = 32;
-            for (int cand : {12, 16, 20, 24, 28, 32}) {
-                int n = 0;
-                for (int j = 0; j < J; ++j) n += (pj[j + 1] - pj[j] + cand - 1) / cand;
-                if (n <= 64) { len = cand; break; }
-            }
-            int ns = 0;
-            for (int j = 0; j < J; ++j) {
-                const int first = ns;
-                for (int b0 = pj[j]; b0 < pj[j + 1]; b0 += len) {
-                    if (ns >= FUSED_MAXSEG) { ok = false; break; }
-                    seg[((size_t)c * FUSED_MAXSEG + ns) * 2] = b0;
-                    seg[((size_t)c * FUSED_MAXSEG + ns) * 2 + 1] = b0 + len < pj[j + 1] ? b0 + len : pj[j + 1];
-                    ++ns;
-                }
-                jseg[(size_t)c * J + j] = first | ((ns - first) << 16);
-            }
-            nseg[c] = ns;
-        }
-        if (ok && J * 4 <= 256 && chunks < 64) {
-            DP_CHECK_HIP(hipMalloc(&h->jl_seg, seg.size() * sizeof(int32_t)));
-            DP_CHECK_HIP(hipMalloc(&h->jl_nseg, nseg.size() * sizeof(int32_t)));
-            DP_CHECK_HIP(hipMalloc(&h->jl_jseg, jseg.size() * sizeof(int32_t)));
-            DP_CHECK_HIP(hipMemcpy(h->jl_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            DP_CHECK_HIP(hipMemcpy(h->jl_nseg, nseg.data(), nseg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            DP_CHECK_HIP(hipMemcpy(h->jl_jseg, jseg.data(), jseg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            h->jl_fused_ok = true;
-        }
-    }
     // dense weight chunks of k_skin_bwd_mfma: W^T[c][joint][local vertex] (entries of one (vertex, joint) pair summed), split hi / lo,
     // stored in the lane order of the MFMA A operand: [chunk][wave = vertex quarter][joint tile][k-step][plane][lane][8 vertices]
     (void)hipFree(h->jl_wfrag);
     h->jl_wfrag = nullptr;
-    h->jl_mfma_ok = false;
+    h->jl_onepass_ok = false;
     {
         bool regular = J <= 64 && chunks >= 1;
         for (int c = 0; c < chunks && regular; ++c) regular = vstart[c] == c * 256;
@@ -2635,7 +2309,11 @@ extern "C" int dposer_lbs_prepare_joint_lists(dposer_body_t h, const int32_t* jp
                                 }
             DP_CHECK_HIP(hipMalloc(&h->jl_wfrag, frag.size() * sizeof(uint16_t)));
             DP_CHECK_HIP(hipMemcpy(h->jl_wfrag, frag.data(), frag.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            h->jl_mfma_ok = true;
+            // the one-pass backward is dispatched to the assets it is measured and tested on: fewer than 64 chunks of at most 1024 list
+            // entries each.  (The lists are the caller's and need not come from a K = 4 skinning table, so neither limit follows from the
+            // dispatch's skin_k == 4.  A limit of 128 runs of <= 32 entries of one joint per chunk adds nothing: at most 1024 / 32 + J <= 96.)
+            h->jl_onepass_ok = chunks < 64;
+            for (int c = 0; c < chunks; ++c) h->jl_onepass_ok = h->jl_onepass_ok && cfirst[c + 1] - cfirst[c] <= 1024;
         }
     }
     h->jl_ready = true;
@@ -3020,8 +2698,8 @@ extern "C" int dposer_lbs_backward(dposer_body_t h, const void* ws_fwd, void* ws
 // per-wave distance sums [batch][ceil(V / 256)][4]
 struct LbsTemporal { int64_t F; float scale; float* part4; };
 static bool lbs_temporal_in_backward_ok(dposer_body_t h, int32_t skin_k, int64_t batch) {
-    return h && !lbs_blend_fp32() && skin_k == 4 && h->jl_ready && h->jl_fused_ok && h->jl_mfma_ok && batch >= lbs_joint_stream_min() &&
-           body_tuning().skin_bwd_fused && body_tuning().skin_bwd_mfma != 0 && (int64_t)h->jl_chunks * 768 >= lbs_cpad(h->d.num_vertices) &&
+    return h && !lbs_blend_fp32() && skin_k == 4 && h->jl_ready && h->jl_onepass_ok && batch >= lbs_joint_stream_min() &&
+           body_tuning().skin_bwd_fused && (int64_t)h->jl_chunks * 768 >= lbs_cpad(h->d.num_vertices) &&
            h->jl_chunks == (int)ceil_div(h->d.num_vertices, 256);
 }
 extern "C" int32_t dposer_lbs_temporal_in_backward_ok(dposer_body_t h, int32_t skin_k, int64_t batch) { return lbs_temporal_in_backward_ok(h, skin_k, batch) ? 1 : 0; }
@@ -3123,9 +2801,9 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
         FK_HIP_LAUNCH(hipGetLastError());
         vg.vslot = fold->vertex_slot; vg.U = fold->n_slots;
     }
-    const bool fused = !blend32 && skin_k == 4 && h->jl_ready && h->jl_fused_ok && batch >= lbs_joint_stream_min() && body_tuning().skin_bwd_fused;
+    const bool fused = !blend32 && skin_k == 4 && h->jl_ready && h->jl_onepass_ok && batch >= lbs_joint_stream_min() && body_tuning().skin_bwd_fused;
     if (fused && (int64_t)h->jl_chunks * 768 >= Cpad) {
-        // the fused kernel writes every coordinate column of every pose: only the 32-row groups that hold padding rows need zeros (a
+        // the one-pass kernel writes every coordinate column of every pose: only the 32-row groups that hold padding rows need zeros (a
         // contiguous tail of each FT array).  The full clear was 516 MB = 91 us per backward at 4096 poses.
         const int64_t r0 = batch & ~(int64_t)31;
         if (r0 < Bpad) {
@@ -3136,7 +2814,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
         DP_CHECK_HIP(hipMemsetAsync(doff, 0, Bpad * Cpad * 4, st));
     }
     const int mfma_g = body_tuning().skin_bwd_mfma;
-    if (fused && mfma_g != 0 && h->jl_mfma_ok) {
+    if (fused) {
         SkinBwdMfmaArgs a;
         a.vg = vg;
         a.dverts = d_verts; a.offsets = offsets; a.ld_off = Cpad; a.v_shaped = v_shaped; a.v_shaped_batched = v_shaped_batched; a.A = A;
@@ -3159,15 +2837,6 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
             if (v_shaped_batched) hipLaunchKernelGGL((k_skin_bwd_mfma<4, true>), dim3((unsigned)ceil_div(batch, 4)), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((k_skin_bwd_mfma<4, false>), dim3((unsigned)ceil_div(batch, 4)), dim3(256), 0, st, a);
         }
-        FK_HIP_LAUNCH(hipGetLastError());
-    } else if (fused) {
-        SkinBwdFusedArgs a;
-        a.vg = vg;
-        a.dverts = d_verts; a.offsets = offsets; a.ld_off = Cpad; a.v_shaped = v_shaped; a.v_shaped_batched = v_shaped_batched; a.A = A;
-        a.skin_idx = skin_idx; a.skin_w = skin_w; a.J = J; a.V = V; a.dvp = d_vposed; a.doff_hi = doff_hi; a.doff_lo = doff_lo; a.Cpad = (int)Cpad;
-        a.cfirst = h->jl_first; a.entry = h->jl_entry; a.seg = reinterpret_cast<const int2*>(h->jl_seg); a.nseg = h->jl_nseg; a.jseg = h->jl_jseg;
-        a.dA = dA; a.chunks = h->jl_chunks; a.B = batch;
-        hipLaunchKernelGGL(k_skin_bwd_fused, dim3((unsigned)batch), dim3(256), 0, st, a);
         FK_HIP_LAUNCH(hipGetLastError());
     } else {
         SkinBwdArgs a;

@@ -141,8 +141,7 @@ template <typename Epi> struct EpiRing<Epi, decltype((void)Epi::kRingPerWave)> {
 // delayed DMA issue for the second wave of each SIMD, register staging, persistent workgroups) are in docs/experiments_rounds_1-4.md (4.1).
 // Epi::apply(params, acc, channel_base, sample_base, lane, wave row id, split, staged params, stride, scratch).
 // One output tile (cblk, sblk) [x one k-split] by the C::THREADS threads whose workgroup-local id is `tid` (the whole workgroup in
-// gemm_ft_kernel; a persistent kernel -- gemm_sampler.hip -- calls it tile after tile, or with two half-workgroups side by side on
-// disjoint LDS regions: the barriers inside are workgroup-wide, so both halves must run the same number of stages).
+// gemm_ft_kernel, its only caller; the barriers inside are workgroup-wide).
 template <typename T, int WC, int WS, int TC, int TS, int KB, typename Epi, int NB>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const typename Epi::Params& ep, int cblk, int sblk, int split, unsigned char* smem, int tid) {
 #ifdef DPOSER_PHASE_STAMPS     // tools/tile_phase_probe.hip: where a tile's time goes (prologue / K loop / epilogue) and when it ran

@@ -30,7 +30,6 @@ hipError_t gemm_bias_silu(int prec, bool train, int shape, const GemmArgs& g, co
 hipError_t gemm_rowmajor(int prec, int shape, const GemmArgs& g, const RowMajorParams& p, hipStream_t st);
 hipError_t gemm_em_step(int prec, int shape, const GemmArgs& g, const EmStepParams& p, hipStream_t st);
 hipError_t gemm_partial_ft(int prec, int shape, const GemmArgs& g, const PartialFTParams& p, hipStream_t st);   // SHAPE_MID, g.ksplit splits of segment 0
-hipError_t gemm_dsm_step(int prec, int shape, const GemmArgs& g, const DsmStepParams& p, hipStream_t st);   // SHAPE_FINAL / SHAPE_FINAL_S
 hipError_t gemm_plain_ft(int prec, int shape, const GemmArgs& g, const PlainFTParams& p, hipStream_t st);
 hipError_t gemm_gn_bwd(int prec, int shape, const GemmArgs& g, const GNBwdParams& p, hipStream_t st, int gs = 32);
 hipError_t gemm_silu_bwd(int prec, int shape, const GemmArgs& g, const SiLUBwdParams& p, hipStream_t st);
@@ -40,43 +39,8 @@ hipError_t gemm_wgrad_tr(int shape, const WgradTrArgs& g, const WgradParams& p, 
 // every 256x256 wgrad tile of a training step in one launch (wgrad_batch.h)
 hipError_t gemm_wgrad_tr_batch(const WgradBatchArgs& a, hipStream_t st);
 
-// ---- persistent Euler-Maruyama sampler (gemm_sampler.hip): one workgroup per block of 256 samples walks every layer of every step
-struct SamplerLayer {
-    const void* W;            // packed layer weights (x-path prefix of the K-concatenated rows)
-    const void* in;           // FT input of the layer (this step's state for layer 0)
-    const void* resid;        // FT residual input or null
-    void* out;                // FT output
-    const float* gamma;
-    const float* beta;
-    int w_stride_blocks;      // k-blocks per packed weight row-block
-    int kblocks;              // k-blocks of the x-path
-};
-struct SamplerArgs {
-    const SamplerLayer* layers;   // DEVICE table [L]
-    int L, H;
-    int64_t Spad;
-    const float* table;           // [n_steps][L][H] time-bias rows
-    const float* tsteps;          // DEVICE [n_steps] t of every step
-    int n_steps;
-    uint32_t step0;               // global index of the first step (Philox offset)
-    const void* Wpost;
-    int post_kblocks;
-    const void* last;             // FT output of the last GroupNorm layer
-    float* x_mean_ft;             // written on the last step
-    EmStepParams em;              // per-step fields (t, step, x_mean_ft) are filled in by the kernel; em.pf carries probability flow
-    // cluster form only (k_sampler_cluster): all zero before the launch
-    uint32_t* progress;           // DEVICE [n_sblk] tiles finished per sample block (4 per layer / update phase)
-    uint32_t* ctrl;               // DEVICE [SAMPLER_CTRL_WORDS]: [0, 8) workgroups seen per XCD, [8] error flag, [9] longest wait in polls
-    int n_sblk;                   // sample blocks of 256
-};
-constexpr int SAMPLER_CTRL_WORDS = 16;
-hipError_t launch_sampler_persistent(int prec, const SamplerArgs& a, int64_t n_sample_blocks, hipStream_t st);
-// four workgroups of one XCD share a sample block: one channel tile each per layer, joined by a counter per block (sync = 0: no waits --
-// a timing probe whose samples are garbage)
-hipError_t launch_sampler_cluster(int prec, const SamplerArgs& a, int sync, hipStream_t st);
-
 // ---- optional per-launch profiling (HIP events on the launch stream; off by default) ------------------
-enum GemmEpiKind : int { EPI_GN = 0, EPI_GN_TRAIN, EPI_BIAS_SILU, EPI_ROWMAJOR, EPI_PLAIN_FT, EPI_GN_BWD, EPI_SILU_BWD, EPI_WGRAD, EPI_EM_STEP, EPI_DSM_STEP, EPI_KINDS };
+enum GemmEpiKind : int { EPI_GN = 0, EPI_GN_TRAIN, EPI_BIAS_SILU, EPI_ROWMAJOR, EPI_PLAIN_FT, EPI_GN_BWD, EPI_SILU_BWD, EPI_WGRAD, EPI_EM_STEP, EPI_KINDS };
 constexpr int GEMM_PROF_KINDS = EPI_KINDS * 3 * GEMM_NSHAPES;      // (epilogue kind, precision, tiling)
 // bf16x3 entry points (gemm_launch_x3.hip): the dispatchers of gemm_launch.hip forward prec == PREC_BF16X3 here
 hipError_t gemm_gn_x3(bool train, int shape, const GemmArgs& g, const GNParams& p, hipStream_t st, int gs = 32);      // every activation, group sizes 16 / 32 / 64

@@ -33,7 +33,7 @@ struct ProfScope {
     }
     ~ProfScope() { if (r) (void)hipEventRecord(r->b, st); }
 };
-const char* kEpiNames[EPI_KINDS] = {"gn_fwd", "gn_fwd_train", "bias_silu", "rowmajor", "plain_ft", "gn_bwd_dgrad", "silu_bwd_dgrad", "wgrad", "post_em_step", "post_dsm_step"};
+const char* kEpiNames[EPI_KINDS] = {"gn_fwd", "gn_fwd_train", "bias_silu", "rowmajor", "plain_ft", "gn_bwd_dgrad", "silu_bwd_dgrad", "wgrad", "post_em_step"};
 const char* kShapeNames[GEMM_NSHAPES] = {"256x256", "128x128", "128x32", "64x128", "64x32", "128x64", "128x64w8"};
 }   // namespace
 void gemm_prof_enable(int on) {
@@ -162,10 +162,6 @@ hipError_t gemm_partial_ft(int prec, int shape, const GemmArgs& g, const Partial
     PROF(EPI_PLAIN_FT);
     if (prec == PREC_BF16X3) return gemm_partial_ft_x3(shape, g, p, st);
     typedef EpiPartialFT<__bf16> A; typedef EpiPartialFT<float> B; DISPATCH(A, B, M_MID | M_SMALL);
-}
-hipError_t gemm_dsm_step(int prec, int shape, const GemmArgs& g, const DsmStepParams& p, hipStream_t st) {
-    PROF(EPI_DSM_STEP);
-    typedef EpiDsm<__bf16> A; typedef EpiDsm<float> B; DISPATCH(A, B, M_FINAL | M_FINAL_S);
 }
 hipError_t gemm_plain_ft(int prec, int shape, const GemmArgs& g, const PlainFTParams& p, hipStream_t st) {
     PROF(EPI_PLAIN_FT);

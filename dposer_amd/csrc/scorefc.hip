@@ -349,45 +349,30 @@ struct ScoreTuning {
     int wgrad_groups = -1;            // DPOSER_WGRAD_GROUPS = n: bucketed backward with the lane launches of n layer groups (0: off)
     int adam_write_through = 1;       // DPOSER_ADAM_WT = 0: plain stores for the optimizer state in the fused optimizer + re-pack kernel (A/B)
     int64_t silu_split_max = 2048;    // DPOSER_SILU_SPLIT_MAX = <samples>: up to this padded batch the time-branch dgrad runs one k-split per layer + a reduce pass (0: never)
-    int dsm_fused = 0;                // DPOSER_DSM_FUSED = 1: post_dense with the DSM loss in its epilogue (EpiDsm) instead of GEMM -> res -> k_dsm
-                                      // (opt-in: measured -0.6 % at 8192 poses, -0.2 % at 65536, +0.5 % at 1280 -- profiles/r04_dsm_fused_ab.txt)
     bool small64 = true;              // DPOSER_SMALL64=0: never the 128x64 / 8-wave tiling (A/B; bit-identical)
     int64_t small64_min = 1024, small64_max = 2048;      // DPOSER_SMALL64_MIN / _MAX: its window, min < padded samples <= max
     int64_t small_tile_max = 2048;    // DPOSER_SMALL_TILE_MAX = <samples>: up to this padded batch the GroupNorm layers take the 128x32 tiling also where 128x128
                                       // divides the batch (1280 samples are 80 workgroups of 128x128 on 256 CUs).  Bit-identical.  Round 6, with three K-loop slots on
                                       // that tiling (gemm_launch.hip): training step 0.370 -> 0.339 ms at 1536 poses, 0.389 -> 0.383 at 2048, slower from 2560
                                       // (profiles/r06_small_tile_max_sweep.md; round 5, two slots: the crossover was 1280, profiles/r05_small_tile_ab.txt)
-    int sampler_persistent = 0;       // DPOSER_SAMPLER_PERSISTENT = 1: one persistent kernel for the plain EM sampler
-    int64_t sampler_persistent_min = 256;
-    void load() {
-        const char* e = getenv("DPOSER_BIG_MIN_BATCH");
-        big_min = e ? atoll(e) : (int64_t)16384;
+    void load() {      // the defaults above, overridden by what the environment sets
+        *this = ScoreTuning{};
+        const char* e;
+        if ((e = getenv("DPOSER_BIG_MIN_BATCH"))) big_min = atoll(e);
         gnbwd_big = env_tri("DPOSER_GNBWD_BIG");
-        e = getenv("DPOSER_FINAL_SMALL_MAX");
-        final_small_max = e ? atoll(e) : (int64_t)16384;
+        if ((e = getenv("DPOSER_FINAL_SMALL_MAX"))) final_small_max = atoll(e);
         wgrad_big = env_tri("DPOSER_WGRAD_BIG");
         wgrad_tr = env_tri("DPOSER_WGRAD_TR");
         wgrad_stream = env_tri("DPOSER_WGRAD_STREAM");
         wgrad_batched = env_tri("DPOSER_WGRAD_BATCHED");
         wgrad_layer_lanes = env_tri("DPOSER_WGRAD_LAYER_LANES");
-        e = getenv("DPOSER_WGRAD_GROUPS");
-        wgrad_groups = e ? atoi(e) : -1;
-        adam_write_through = env_tri("DPOSER_ADAM_WT") == 0 ? 0 : 1;
-        dsm_fused = env_tri("DPOSER_DSM_FUSED") == 1 ? 1 : 0;
-        e = getenv("DPOSER_SILU_SPLIT_MAX");
-        silu_split_max = e ? atoll(e) : (int64_t)2048;
-        e = getenv("DPOSER_SMALL64");
-        small64 = !(e && e[0] == '0');
-        e = getenv("DPOSER_SMALL64_MIN");
-        small64_min = e ? atoll(e) : (int64_t)1024;
-        e = getenv("DPOSER_SMALL64_MAX");
-        small64_max = e ? atoll(e) : (int64_t)2048;
-        e = getenv("DPOSER_SMALL_TILE_MAX");
-        small_tile_max = e ? atoll(e) : (int64_t)2048;
-        e = getenv("DPOSER_SAMPLER_PERSISTENT");
-        sampler_persistent = e ? atoi(e) : 0;
-        e = getenv("DPOSER_SAMPLER_PERSISTENT_MIN");
-        sampler_persistent_min = e ? atoll(e) : (int64_t)256;
+        if ((e = getenv("DPOSER_WGRAD_GROUPS"))) wgrad_groups = atoi(e);
+        if (env_tri("DPOSER_ADAM_WT") == 0) adam_write_through = 0;
+        if ((e = getenv("DPOSER_SILU_SPLIT_MAX"))) silu_split_max = atoll(e);
+        if ((e = getenv("DPOSER_SMALL64")) && e[0] == '0') small64 = false;
+        if ((e = getenv("DPOSER_SMALL64_MIN"))) small64_min = atoll(e);
+        if ((e = getenv("DPOSER_SMALL64_MAX"))) small64_max = atoll(e);
+        if ((e = getenv("DPOSER_SMALL_TILE_MAX"))) small_tile_max = atoll(e);
     }
 };
 static ScoreTuning& score_tuning() {
@@ -443,9 +428,6 @@ struct Ws {
     // shared-t time table
     int64_t npad;
     float *tt_labels, *tt_emb, *tt_temb, *table;
-    float* tt_t;                   // t of every step (persistent sampler)
-    SamplerLayer* smp_layers;      // device table of the persistent sampler's per-layer operands
-    uint32_t* smp_sync;            // cluster sampler: control words + one progress counter per block of 256 samples
     // transposed copies / partials / slabs (training)
     char *dyT[MAX_L], *hT[MAX_L], *tembT, *embT, *xinT, *dresT, *dUT;
     float *gn_part[MAX_L], *cs_part_post, *cs_part_se, *silu_part, *slabs, *dU_part;
@@ -516,9 +498,6 @@ static void layout_ws(const dposer_scorefc_s* h, int64_t B, int mode, int n_step
         w.tt_emb = (float*)take(w.npad * E * 4);
         w.tt_temb = (float*)take(w.npad * E * 4);
         w.table = (float*)take(w.npad * (int64_t)L * H * 4);
-        w.tt_t = (float*)take(w.npad * 4);
-        w.smp_layers = (SamplerLayer*)take(MAX_L * sizeof(SamplerLayer));
-        w.smp_sync = (uint32_t*)take((SAMPLER_CTRL_WORDS + Bpad / 256 + 1) * 4);
     } else {
         w.emb = take(Bpad * E * esz);
         w.temb = take(Bpad * E * esz);
@@ -552,7 +531,7 @@ static void layout_ws(const dposer_scorefc_s* h, int64_t B, int mode, int n_step
             w.dUT = take(Bpad * E * esz);
         }
         const int64_t nchunks = ceil_div(Bpad, 2048);
-        w.cs_part_post = (float*)take(cs_post_rows(Bpad) * h->Cp * 4);      // rows: k_colsum chunks, k_dsm's blocks (<= 1024) or EpiDsm's wave rows (Bpad / 32)
+        w.cs_part_post = (float*)take(cs_post_rows(Bpad) * h->Cp * 4);      // rows: k_colsum's chunks (Bpad / 2048) or k_dsm's blocks (<= 1024)
         w.cs_part_se = (float*)take(nchunks * E * 4);
         w.silu_part = (float*)take(silu_part_rows(Bpad, h->x3) * (int64_t)E * 4);       // per-wave column sums of dU (time-branch dgrad epilogue), or k_silu_bwd_reduce's per-block sums
         // slabs: worst case ksplit 32 is never reached for the big tensors; size exactly below
@@ -954,65 +933,6 @@ static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* pa
     const bool fused = !observation && (pf || !noise) && !traj && h->Cp == h->Dpad;
     if (fused) ea.x_ft = w.xft;
     DP_HIP_LAUNCH(launch_em_update(ea, st));
-    // Persistent form of the fast path (gemm_sampler.hip): one workgroup per 256 samples walks every layer of every step -- no
-    // grid-wide join per layer, no launch per layer.  Same kernels' code per tile: bit-identical samples (tested).  Needs the
-    // 256 x 256 tiling (hidden_dim 1024 groups, batch padded to 256) and the 64-channel post_dense tile.
-    // OFF by default (DPOSER_SAMPLER_PERSISTENT=1 enables it): measured (tools/sampler_ab.py, profiles/r03_sampler_ab.txt)
-    //   65536 samples: 715 us per step against 680 us for the six launches;  32768 / 16384 samples: 453 us against 341 / 182 us.
-    // A workgroup alone on its CU needs 453 us per step (26 us per 256 x 256 x 1024 tile) however few of them run -- so below 256
-    // blocks the launches win by using every CU -- and at 256 blocks the same work takes 715 us: a workgroup re-reads its 512 KB
-    // input panel for each of the 4 channel tiles (the launches let 4 tiles on one XCD share it through L2), 3.3 GB per step
-    // through MALL / HBM, under the chip's power cap.  Removing the grid-wide joins does not pay for that.
-    const int persistent_env = score_tuning().sampler_persistent;
-    const int64_t persistent_min = score_tuning().sampler_persistent_min;
-    if (fused && persistent_env && !(sc.kind == SDE_VP && sc.discrete) && !h->x3 && h->d.activation == DPOSER_ACT_SWISH && h->gs == 32 && h->H % 256 == 0 && h->Cp == 64 && w.Bpad % 256 == 0 && (persistent_env >= 2 || w.Bpad >= persistent_min)) {
-        SamplerLayer tab[MAX_L];
-        std::memset(tab, 0, sizeof(tab));
-        for (int l = 0; l < h->L; ++l) {
-            const LayerOff& lo = h->layer[l];
-            tab[l].W = packed + h->pk_wl[l];
-            tab[l].in = l == 0 ? (const void*)w.xin : (const void*)w.hbuf[(l - 1) % 3];
-            tab[l].resid = (l >= 2 && (l % 2) == 0) ? w.hbuf[(l - 2) % 3] : nullptr;
-            tab[l].out = w.hbuf[l % 3];
-            tab[l].gamma = flat + lo.gamma;
-            tab[l].beta = flat + lo.beta;
-            tab[l].w_stride_blocks = (lo.kin_pad + h->E) / h->KBS;
-            tab[l].kblocks = lo.kin_pad / h->KBS;
-        }
-        DP_CHECK_HIP(hipMemcpyAsync(w.smp_layers, tab, sizeof(SamplerLayer) * h->L, hipMemcpyHostToDevice, st));
-        DP_CHECK_HIP(hipMemcpyAsync(w.tt_t, timesteps_host + start_step, n_run * sizeof(float), hipMemcpyHostToDevice, st));
-        // (both copies come from host memory that must stay valid until they have executed: pageable -> the runtime stages them
-        //  before returning; `tab` lives on this stack frame)
-        SamplerArgs sa;
-        std::memset(&sa, 0, sizeof(sa));
-        sa.layers = w.smp_layers; sa.L = h->L; sa.H = h->H; sa.Spad = w.Bpad; sa.table = w.table; sa.tsteps = w.tt_t; sa.n_steps = n_run;
-        sa.step0 = (uint32_t)start_step; sa.Wpost = packed + h->pk_wpost; sa.post_kblocks = h->H / h->KBS; sa.last = w.hbuf[(h->L - 1) % 3];
-        sa.x_mean_ft = w.xmft;
-        EmStepParams& p = sa.em;
-        p.bias = flat + h->off_post_b; p.x_ft = w.xft; p.x_mean_ft = nullptr; p.xin = w.xin;
-        p.sigmas = sigmas; p.sde = make_sde_dev(sc); p.t = 0.f; p.num_scales = h->d.num_scales;
-        p.scale_by_sigma = sbs_mode(h); p.D = h->D; p.Cp = h->Cp; p.QD = (h->D + 3) >> 2; p.S_valid = B;
-        p.seed = seed; p.step = 0; p.pf = pf;     // (the persistent kernels copy these fields into every step's EpiEmStep: PF is carried)
-        if (persistent_env >= 2) {
-            // cluster form (gemm_sampler.hip): 2 = joined by the per-block counters, 3 = the same walk without waits (timing probe, garbage samples)
-            sa.n_sblk = (int)(w.Bpad / 256);
-            sa.ctrl = w.smp_sync; sa.progress = w.smp_sync + SAMPLER_CTRL_WORDS;
-            DP_CHECK_HIP(hipMemsetAsync(w.smp_sync, 0, (SAMPLER_CTRL_WORDS + sa.n_sblk) * 4, st));
-            DP_HIP_LAUNCH(launch_sampler_cluster(h->f32 ? PREC_FP32 : PREC_BF16, sa, persistent_env == 2, st));
-            DP_HIP_LAUNCH(launch_ft_to_rows(w.xft, x, w.xmft, x_mean, B, w.Bpad, h->D, h->Dpad, st));
-            uint32_t ctrl[SAMPLER_CTRL_WORDS];
-            DP_CHECK_HIP(hipMemcpyAsync(ctrl, w.smp_sync, sizeof(ctrl), hipMemcpyDeviceToHost, st));
-            DP_CHECK_HIP(hipStreamSynchronize(st));
-            if (getenv("DPOSER_SAMPLER_CLUSTER_REPORT"))
-                fprintf(stderr, "[dposer] cluster sampler: workgroups per XCD %u %u %u %u %u %u %u %u, error %u, longest wait %u polls\n",
-                        ctrl[0], ctrl[1], ctrl[2], ctrl[3], ctrl[4], ctrl[5], ctrl[6], ctrl[7], ctrl[8], ctrl[9]);
-            if (ctrl[8]) return dposer_set_error(DPOSER_ERR_HIP, std::string("cluster sampler: ") + (ctrl[8] == 2 ? "workgroups not dealt evenly to the XCDs" : "a workgroup waited past its poll budget (not all resident?)"));
-            return DPOSER_OK;
-        }
-        DP_HIP_LAUNCH(launch_sampler_persistent(h->f32 ? PREC_FP32 : PREC_BF16, sa, w.Bpad / 256, st));
-        DP_HIP_LAUNCH(launch_ft_to_rows(w.xft, x, w.xmft, x_mean, B, w.Bpad, h->D, h->Dpad, st));
-        return DPOSER_OK;
-    }
     if (fused) {
         const int shape = final_shape(w.Bpad);
         for (int i = 0; i < n_run; ++i) {
@@ -1460,7 +1380,7 @@ static int run_wgrad(dposer_scorefc_s* h, const void* dyT, int n_rows_pad, int n
 
 // forward in training layout: every layer input / normalised activation is kept for the backward pass
 static int forward_core_train(dposer_scorefc_s* h, const float* flat, const char* packed, Ws& w, int64_t B, bool dropout_on, uint64_t seed,
-                              uint32_t step, hipStream_t st, bool with_post = true) {
+                              uint32_t step, hipStream_t st) {
     const int L = h->L;
     const bool tr = wgrad_tr_mode(h, w.Bpad);   // then no wgrad reads a transposed activation
     DP_TRY(run_temb(h, flat, packed, w, w.upre, tr ? nullptr : w.tembT, true, st));
@@ -1487,7 +1407,6 @@ static int forward_core_train(dposer_scorefc_s* h, const float* flat, const char
         if (h->x3 && !((l % 2) == 0 && l + 2 < L)) p.out = nullptr;
         DP_HIP_LAUNCH(gemm_gn(gemm_prec(h), true, shape, g, p, st, h->gs));
     }
-    if (!with_post) return DPOSER_OK;      // (the fused DSM step runs post_dense itself, with the loss in its epilogue)
     return run_post(h, flat, packed, w.hbuf[L - 1], w.p_h[L - 1], w.res, B, w.Bpad, st);
 }
 
@@ -1996,28 +1915,8 @@ static int dsm_loss_fwd_bwd_impl(dposer_scorefc_t h, const float* flat, const vo
     pa.B = B; pa.Bpad = Bpad; pa.D = h->D; pa.Dpad = h->Dpad; pa.E = h->E; pa.fourier = h->d.embedding == DPOSER_EMB_FOURIER; pa.f32 = h->f32; pa.sde = sc; pa.eps = eps;
     pa.seed = seed; pa.step = step;
     DP_HIP_LAUNCH(launch_prep_train(pa, st));
-    // post_dense + loss + d loss / d res: one launch (EpiDsm) while its partials fit the step's buffers, else GEMM -> res -> k_dsm
-    const int pshape = final_shape(Bpad);
-    const int64_t prow = (Bpad / (shape_st(pshape) * 32)) * shape_ws(pshape);                 // wave rows = column-sum partial rows
-    const int chan_waves = pshape == SHAPE_FINAL ? 1 : 2;                                    // waves side by side over the 64 channels
-    const bool fused_post = score_tuning().dsm_fused && !h->x3 && sde->kind != DPOSER_SDE_VE && h->Cp == 64 && prow * chan_waves <= 8192 && prow <= cs_post_rows(Bpad);
-    DP_TRY(forward_core_train(h, flat, packed, w, B, true, seed, step, st, !fused_post));
+    DP_TRY(forward_core_train(h, flat, packed, w, B, true, seed, step, st));
     int nb = 0;
-    if (fused_post) {
-        g_next_flops = 2.0 * (double)B * h->D * h->H;
-        GemmArgs g = gemm_args(packed + h->pk_wpost, h->H / h->KBS, h->Cp / (shape_ct(pshape) * 32), (int)(Bpad / (shape_st(pshape) * 32)));
-        add_seg(g, w.hbuf[h->L - 1], h->H / h->KBS);
-        DsmStepParams p;
-        std::memset(&p, 0, sizeof(p));
-        p.bias = flat + h->off_post_b; p.t = w.tbuf; p.z = w.zbuf; p.sigmas = sigmas; p.dres = w.dres; p.loss_part = w.loss_part;
-        p.cs_part = w.cs_part_post; p.sde = make_sde_dev(sc); p.grad_scale = (float)(1.0 / ((double)B * (double)h->D));
-        p.num_scales = h->d.num_scales; p.scale_by_sigma = h->d.scale_by_sigma; p.fourier = h->d.embedding == DPOSER_EMB_FOURIER;
-        p.D = h->D; p.Dpad = h->Dpad; p.Cp = h->Cp; p.S_valid = B;
-        DP_HIP_LAUNCH(gemm_dsm_step(h->f32 ? PREC_FP32 : PREC_BF16, pshape, g, p, st));
-        nb = (int)(prow * chan_waves);
-        const SumJob loss_sum{w.loss_part, nb, loss};
-        return backward_core(h, flat, packed, w, B, true, seed, step, flat_grad, nullptr, sink, st, &loss_sum, (int)prow);
-    }
     DsmArgs da;
     da.res = w.res; da.t = w.tbuf; da.z = w.zbuf; da.sigmas = sigmas; da.dres = w.dres; da.loss_part = w.loss_part; da.B = B; da.Bpad = Bpad;
     da.cs_part = w.cs_part_post;

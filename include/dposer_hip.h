@@ -101,8 +101,8 @@ int64_t dposer_scorefc_packed_bytes(dposer_scorefc_t h, int32_t with_backward);
 int dposer_scorefc_pack(dposer_scorefc_t h, const float* flat_params, void* packed, int32_t with_backward, void* stream);
 /* Re-reads the A/B environment switches of the score path (DPOSER_BIG_MIN_BATCH, DPOSER_GNBWD_BIG, DPOSER_WGRAD_BIG, DPOSER_WGRAD_TR,
  * DPOSER_WGRAD_STREAM, DPOSER_WGRAD_BATCHED, DPOSER_SMALL_TILE_MAX, DPOSER_WGRAD_LAYER_LANES, DPOSER_WGRAD_GROUPS, DPOSER_FINAL_SMALL_MAX,
- * DPOSER_SAMPLER_PERSISTENT[_MIN], DPOSER_ADAM_WT, DPOSER_DSM_FUSED, DPOSER_SILU_SPLIT_MAX); they are otherwise read ONCE per
- * process (first use), never per call. */
+ * DPOSER_ADAM_WT, DPOSER_SILU_SPLIT_MAX, DPOSER_SMALL64, DPOSER_SMALL64_MIN / _MAX); they are otherwise read ONCE per process (first use),
+ * never per call. */
 void dposer_scorefc_tuning_reload(void);
 /* TEST HOOK: dropout keep decisions of every site as bytes [n_layers][batch][hidden_dim] (device memory, NULL = back to the Philox
  * streams), used by the training epilogues of calls with exactly this batch size (hidden_dim 1024).  It lets a parity test run the
@@ -144,8 +144,7 @@ int dposer_em_sampler(dposer_scorefc_t h, const float* flat_params, const void* 
  * Arguments and noise layout are dposer_em_sampler's, so a trace recorded from the reference maps onto the call unchanged:
  * the predictor slot of each step is present and never read (no predictor normal is drawn); with completion the two
  * imputation slots are read (or drawn in-kernel), since the reference imputes with randn under probability flow too
- * (sampling.py:416-420).  Without observation and trajectory the call takes the one-launch-per-step fused form; the opt-in
- * persistent kernels (DPOSER_SAMPLER_PERSISTENT) carry the flag as well. */
+ * (sampling.py:416-420).  Without observation and trajectory the call takes the one-launch-per-step fused form. */
 int dposer_pf_sampler(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws,
                       const dposer_sde_desc* sde, float* x, float* x_mean, const float* timesteps_host,
                       int32_t start_step, const float* observation, const float* mask, const float* noise,

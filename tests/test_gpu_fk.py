@@ -450,9 +450,9 @@ def test_row_concatenated_blend_gradient_launch_keeps_every_bit(bm, tuning_env, 
 
 
 def test_fused_skinning_backward_agrees_with_the_two_kernel_path(bm, monkeypatch):
-    """The one-pass skinning-backward kernels -- k_skin_bwd_mfma (default: the joint reduction as dense 16x16x32 MFMAs on bf16 hi / lo
-    planes, a workgroup per four poses) and k_skin_bwd_fused (one streaming pass per pose: d_verts read once, v_posed never in HBM, joint
-    lists in balanced segments) -- against k_skin_bwd + k_skin_bwd_joints: same terms, other summation orders.  B = 70: the first 64 poses go through the permuted block -> pose map, the rest through the identity tail; betas require a
+    """The one-pass skinning-backward kernel k_skin_bwd_mfma (the joint reduction as dense 16x16x32 MFMAs on bf16 hi / lo planes; d_verts
+    read once, v_posed never in HBM), with four (default) and with two poses per workgroup, against k_skin_bwd + k_skin_bwd_joints: same
+    terms, other summation orders.  B = 70 is no multiple of four, so the default's last workgroup is partly masked; betas require a
     gradient, so d v_posed is written too."""
     B = 70
     rs = np.random.RandomState(12)
@@ -472,21 +472,19 @@ def test_fused_skinning_backward_agrees_with_the_two_kernel_path(bm, monkeypatch
     mfma = run()                                       # default: k_skin_bwd_mfma (joint reduction on the matrix pipe, four poses per workgroup)
     monkeypatch.setenv("DPOSER_SKIN_BWD_MFMA", "2")
     mfma2 = run()                                      # ... two poses per workgroup
-    monkeypatch.setenv("DPOSER_SKIN_BWD_MFMA", "0")
-    fused = run()                                      # k_skin_bwd_fused (joint lists walked through LDS)
     monkeypatch.setenv("DPOSER_SKIN_BWD_FUSED", "0")
     two = run()
     monkeypatch.delenv("DPOSER_SKIN_BWD_FUSED")
     monkeypatch.delenv("DPOSER_SKIN_BWD_MFMA")
     monkeypatch.delenv("DPOSER_LBS_JOINT_STREAM_MIN")
     _reload_tuning()
-    for tag, got in (("mfma", mfma), ("mfma, 2 poses", mfma2), ("fused", fused)):
+    for tag, got in (("mfma", mfma), ("mfma, 2 poses", mfma2)):
         for name, a, b in (("d pose", got[0], two[0]), ("d betas", got[1], two[1])):
             err = np.linalg.norm(a - b) / np.linalg.norm(b)
             _log_measured(f"{tag} skinning backward vs two kernels, {name}", err)
-            assert err < 1e-5, (tag, name, err)        # measured: fused 2e-7 / 1e-7, mfma 3e-6 (bf16 hi / lo split products)
+            assert err < 1e-5, (tag, name, err)        # measured: 3e-6 (bf16 hi / lo split products)
             assert np.isfinite(a).all()
-    assert not np.array_equal(fused[0], two[0]) and not np.array_equal(mfma[0], fused[0])        # (they really are other kernels)
+    assert not np.array_equal(mfma[0], two[0])                                                   # (they really are other kernels)
     assert np.array_equal(mfma[0], mfma2[0]) and np.array_equal(mfma[1], mfma2[1])               # the workgroup's pose count changes no sum
 
 

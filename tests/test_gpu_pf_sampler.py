@@ -1,9 +1,7 @@
 """GPU tests of the probability-flow sampler (dposer_pf_sampler: pc_sampler with probability_flow = True, Euler-Maruyama predictor,
 corrector 'none') and of the interpolation task built on it: parity with the reference's own deterministic sampler (golden g28), the
 discrete score functions and the Fourier embedding against the PF oracle loop (tests/pf_ref.py), determinism, the two kernel forms
-(fused epilogue / update kernel), the host routing, the opt-in persistent kernels and tasks/interpolation.py."""
-import os
-
+(fused epilogue / update kernel), the host routing and tasks/interpolation.py."""
 import numpy as np
 import pytest
 import torch
@@ -184,34 +182,6 @@ def test_pc_sampler_probability_flow_never_reaches_the_generic_predictor(monkeyp
     fn = sampling.get_sampling_fn(cfg, _sde("subvp", 8), (16, 63), lambda v: v, 1e-3, device=DEV)
     with pytest.raises(AssertionError, match="generic predictor"):
         fn(m, z=_dev(g["subvp8_z0"]))
-
-
-def test_pf_persistent_kernels_carry_the_flag():
-    """DPOSER_SAMPLER_PERSISTENT=1 (opt-in, gemm_sampler.hip) copies EmStepParams -- the PF flag included -- into every step: the same
-    bits as the per-step launches (child processes: the switch is read once)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, hashlib, torch; sys.path.insert(0, 'tests'); sys.path.insert(0, 'tests/golden'); sys.path.insert(0, '.')\n"
-            "from gpu_common import make_model\n"
-            "from dposer_amd.algorithms.advanced import sampling, sde_lib\n"
-            "for prec, B in (('bf16', 700), ('fp32', 700)):\n"
-            "    cfg, m, p = make_model(3, precision=prec)\n"
-            "    cfg.sampling.probability_flow = True\n"
-            "    sde = sde_lib.subVPSDE(0.1, 20.0, 13)\n"
-            "    fn = sampling.get_sampling_fn(cfg, sde, (B, 63), lambda v: v, 1e-5, device='cuda:0')\n"
-            "    z = torch.randn(B, 63, device='cuda:0', generator=torch.Generator(device='cuda:0').manual_seed(5))\n"
-            "    _, x = fn(m, z=z, seed=11, traj_stride=0)\n"
-            "    _, xs = fn(m, z=z, seed=11, traj_stride=1)\n"
-            "    print('SHA', prec, B, hashlib.sha1(x.cpu().numpy().tobytes()).hexdigest(), bool(torch.isfinite(x).all()), bool(torch.equal(x, xs)))\n")
-    outs = {}
-    for flag in ("0", "1"):
-        r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, DPOSER_SAMPLER_PERSISTENT=flag), capture_output=True,
-                           text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[flag] = [l for l in r.stdout.splitlines() if l.startswith("SHA")]
-        assert len(outs[flag]) == 2 and all(l.endswith("True True") for l in outs[flag]), outs[flag]
-    assert outs["0"] == outs["1"]
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])

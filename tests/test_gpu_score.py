@@ -823,8 +823,6 @@ def test_integration_md_ctypes_stub_runs():
     {"DPOSER_WGRAD_TR": "0"},                                                                # bf16 wgrads on transposed copies
     {"DPOSER_WGRAD_STREAM": "1", "DPOSER_WGRAD_BATCHED": "0"},                                                  # wgrads on the second stream (default 8192..16384)
     {"DPOSER_WGRAD_BATCHED": "1"},                                                           # all 256x256 wgrad tiles in one launch (the single-GPU default)
-    {"DPOSER_DSM_FUSED": "1"},                                                               # post_dense with the loss in its epilogue (opt-in) instead of GEMM -> res -> k_dsm
-    {"DPOSER_DSM_FUSED": "1", "DPOSER_FINAL_SMALL_MAX": "0"},                                # ... and that launch on the 64 x 128 tiling at small batches too
 ])
 def test_alternative_tilings_and_streams_keep_parity(env):
     """The tiling / stream policy depends on the batch size (256x256 GroupNorm-backward and wgrad tiles from 32768 samples,
@@ -867,31 +865,6 @@ def test_layer_split_time_branch_dgrad_matches_the_one_launch_form(B, prec, tuni
             assert rel_err(t2n(a), t2n(b)) < (2e-6 if prec == "fp32" else 2e-3), name     # bf16: dU is rounded to bf16 after the sum
         else:
             assert torch.equal(a, b), name
-
-
-@pytest.mark.parametrize("B,prec", [(700, "fp32"), (8192, "bf16"), (20000, "bf16"), (640, "bf16")])
-def test_loss_in_the_post_dense_epilogue_matches_the_two_launch_form(B, prec, tuning_env):
-    """post_dense + DSM loss + d loss / d res as ONE launch (EpiDsm, opt-in: DPOSER_DSM_FUSED=1 -- measured without gain,
-    profiles/r04_dsm_fused_ab.txt) against GEMM -> res -> k_dsm: the same per-element operations, so
-    d res -- and with it every weight gradient -- is bit-identical; the loss and post_dense's bias gradient are the same sums in
-    another order (per wave tile instead of per block)."""
-    cfg, m, p = make_model(12, precision=prec, dropout=0.1)
-    m.train()
-    rs = np.random.RandomState(4)
-    batch = _dev(rs.standard_normal((B, 63)).astype(np.float32))
-    out = {}
-    for flag in ("1", "0"):
-        tuning_env(DPOSER_DSM_FUSED=flag)
-        out[flag] = _fused_grad(m, batch, None, None, step=3)
-    (l1, g1), (l0, g0) = out["1"], out["0"]
-    assert abs(l1 - l0) / abs(l0) < 1e-6
-    names = [n for n, _ in m.named_parameters()]
-    ib = names.index("post_dense.bias")
-    ob, nbias = m._offsets[ib], 63
-    mask = torch.ones_like(g1, dtype=torch.bool)
-    mask[ob:ob + nbias] = False
-    assert torch.equal(g1[mask], g0[mask])
-    assert rel_err(t2n(g1[ob:ob + nbias]), t2n(g0[ob:ob + nbias])) < 1e-5
 
 
 @pytest.mark.parametrize("B", [8192, 5000, 32768])
@@ -1510,39 +1483,6 @@ def test_ve_probability_flow_ode_on_the_fused_right_hand_side(monkeypatch):
     assert 0 < f[2] and abs(f[2] - u[2]) <= 0.1 * u[2]
     assert np.isfinite(f[0]).all() and np.isfinite(f[4]).all()
     assert rel_err(f[0], u[0]) < 1e-4 and rel_err(f[1], u[1]) < 1e-3
-
-
-def test_persistent_sampler_kernels_return_the_bits_of_the_launch_path():
-    """gemm_sampler.hip (opt-in): DPOSER_SAMPLER_PERSISTENT=1 -- one workgroup per 256 samples walks every layer of every step;
-    =2 -- clusters of four workgroups on one XCD take one channel tile each and are joined by a progress counter per sample block.
-    The same tile code as the per-layer launches, so the samples must be bit-identical -- at 3 sample blocks (one per cluster: the
-    counter is a 4-way barrier per layer) and at 129 (two or three per cluster: members run ahead of each other); child processes
-    (the switch is read once).  13 steps: t = 0.334 is among them, where a contracted `m2b0 * t - db * (t * t)` is one ulp off the
-    unfused value -- the three kernels once disagreed there because hipcc fused it in two of them (csrc/sde_dev.h)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, hashlib, torch; sys.path.insert(0, 'tests'); sys.path.insert(0, 'tests/golden'); sys.path.insert(0, '.')\n"
-            "from gpu_common import make_model\n"
-            "from dposer_amd.algorithms.advanced import sampling, sde_lib\n"
-            "for prec, B in (('bf16', 700), ('fp32', 700), ('bf16', 33000), ('fp32', 16500)):\n"
-            "    cfg, m, p = make_model(3, precision=prec)\n"
-            "    m.eval()\n"
-            "    sde = sde_lib.subVPSDE(0.1, 20.0, 13)\n"
-            "    fn = sampling.get_sampling_fn(cfg, sde, (B, 63), lambda v: v, 1e-3, device='cuda:0')\n"
-            "    z = torch.randn(B, 63, device='cuda:0', generator=torch.Generator(device='cuda:0').manual_seed(5))\n"
-            "    for rep in range(2):\n"
-            "        _, x = fn(m, z=z, seed=11, traj_stride=0)\n"
-            "        print('SHA', prec, B, hashlib.sha1(x.cpu().numpy().tobytes()).hexdigest(), bool(torch.isfinite(x).all()))\n")
-    outs = {}
-    for flag in ("0", "1", "2"):
-        r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, DPOSER_SAMPLER_PERSISTENT=flag), capture_output=True,
-                           text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[flag] = [l for l in r.stdout.splitlines() if l.startswith("SHA")]
-        assert len(outs[flag]) == 8 and all(l.endswith("True") for l in outs[flag])
-    assert outs["0"] == outs["1"]
-    assert outs["0"] == outs["2"]
 
 
 @pytest.mark.parametrize("act", ["elu", "relu", "lrelu"])

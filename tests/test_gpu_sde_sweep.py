@@ -500,7 +500,7 @@ def test_completion_adam_step_every_10th_t(kind, N, scale, B, D):
 
 def _pf_step_sweep(kind, N, scale, B, D, t32):
     """dposer_pf_sampler from start_step = N - 1: ONE probability-flow step.  Without observation and trajectory this is the fused form --
-    post_dense and the Euler-Maruyama update in the GEMM epilogue (gemm_sampler.hip, post_em_step), which carries its own copy of the
+    post_dense and the Euler-Maruyama update in the GEMM epilogue (EpiEmStep, post_em_step), which carries its own copy of the
     update.  The time table is laid out so that its entry N - 1 is the t under test."""
     from dposer_amd import _C
     m, c = _model(D, scale)
@@ -531,12 +531,12 @@ def test_fused_pf_step_other_shapes(kind, N, scale):
     _pf_step_sweep(kind, N, scale, 33, 126, _times(N, every=10))
 
 
-# ---- in-kernel noise, and the persistent forms of the fused sampler ---------------------------------------------------------------------
+# ---- in-kernel noise -----------------------------------------------------------------------------------------------------------------
 def _em_drawn_case(kind, N, scale, B, D, with_traj):
     """dposer_em_sampler_steps with noise = None, ONE step at each of three t (start_step = 0, 1, 2 of a three-entry time list, so the
     Philox offset of the draw is the step index): x_mean, which holds no draw, and x = x_mean + g sqrt(dt) z with z regenerated from
     oracle/philox.py (`_drawn_normals`, STREAM_EM_NOISE).  Without a trajectory buffer this is the fused form, the draw made in the GEMM
-    epilogue (or, where DPOSER_SAMPLER_PERSISTENT selects them, in the persistent kernels); with one, k_em_update draws."""
+    epilogue; with one, k_em_update draws."""
     from dposer_amd import _C
     from oracle import philox as PH
     m, c = _model(D, scale)
@@ -565,40 +565,6 @@ def _em_drawn_case(kind, N, scale, B, D, with_traj):
 @pytest.mark.parametrize("kind,N,scale", CASES, ids=_ids(CASES))
 def test_em_step_with_in_kernel_noise(kind, N, scale, with_traj):
     _em_drawn_case(kind, N, scale, 33, 63, with_traj)
-
-
-def _persistent_child():
-    """Runs in a child process whose DPOSER_SAMPLER_PERSISTENT selects a persistent form (the switch is read once per process): one
-    probability-flow step at every 50th grid value and every edge value, and one Euler-Maruyama step with in-kernel noise at three t,
-    for every kind, at 513 samples: the batch is padded to 768, three sample blocks of 256 (the persistent forms need a padded batch
-    that is a multiple of 256; up to 512 samples the padding is to 64).  Discrete VP is not taken by the persistent kernels
-    (scorefc.hip) and runs the launches here as well."""
-    for kind, N, scale in CASES:
-        _pf_step_sweep(kind, N, scale, 513, 63, _times(N, every=50))
-        _em_drawn_case(kind, N, scale, 513, 63, False)
-    print("PERSISTENT-CHILD-DONE")
-
-
-@pytest.mark.parametrize("mode", ["1", "2"])
-def test_persistent_sampler_forms_stay_inside_the_band(mode):
-    """gemm_sampler.hip: DPOSER_SAMPLER_PERSISTENT = 1 (one workgroup per 256 samples walks every layer of every step) and = 2 (clusters of
-    four workgroups joined by a progress counter) carry their own copy of the Euler-Maruyama epilogue.  They keep the state on the device
-    and write no trajectory, so teacher forcing takes the form of single steps from a given state -- which is what the reference of a
-    teacher-forced run recomputes.  Mode 2 reports on stderr that the cluster kernel ran."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys; sys.path[:0] = ['tests', 'tests/golden', '.']\n"
-            "import test_gpu_sde_sweep as T\n"
-            "T._persistent_child()\n")
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, DPOSER_SAMPLER_PERSISTENT=mode, DPOSER_SAMPLER_CLUSTER_REPORT="1"))
-    print(r.stdout[-6000:])
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "PERSISTENT-CHILD-DONE" in r.stdout
-    if mode == "2":
-        assert "cluster sampler" in r.stderr
 
 
 # ---- shared t, every 10th t: the multi-step (DDIM) estimate --------------------------------------------------------------------------

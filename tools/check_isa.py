@@ -3,7 +3,7 @@
 (run after touching any kernel with inline asm; `python tools/check_isa.py [--keep DIR]`, ~2-3 min: every .hip of dposer_amd/csrc is
 cross-compiled to gfx950 ISA with the Makefile's flags, in parallel).
 
-1. K-loop accumulators (gemm_launch.hip, gemm_sampler.hip): the MFMAs of the hand-placed stage statements are invisible to hipcc's
+1. K-loop accumulators (gemm_launch.hip, gemm_launch_x3.hip): the MFMAs of the hand-placed stage statements are invisible to hipcc's
    hazard recogniser, so between two neighbouring stage statements nothing may read or write an ACCUMULATOR register (a register copy
    there would read an XDL result before its wait states have passed), and those kernels must not spill.
 
@@ -25,12 +25,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dposer_amd", "csrc")
-CONTRACT_OK = {"gemm_launch.hip", "gemm_launch_x3.hip", "gemm_sampler.hip"}          # (Makefile: everything else is built with -ffp-contract=off)
+CONTRACT_OK = {"gemm_launch.hip", "gemm_launch_x3.hip"}          # (Makefile: everything else is built with -ffp-contract=off)
 
-# the opt-in persistent / cluster samplers (DPOSER_SAMPLER_PERSISTENT=1 / =2, off by default: measured slower, profiles/r05_sampler_small_ab.txt)
-# keep 3..8 registers of their prologue in scratch (12..28 bytes per lane); nothing between their stage statements touches scratch (that
-# check still applies to them)
-SPILL_NOTED = re.compile(r"k_sampler_(persistent|cluster)")
 M0_READER = re.compile(r"^(global_load_lds|s_movrel|v_movrel|ds_gws|s_sendmsg)")
 
 
@@ -199,7 +195,7 @@ def regs(line):
     return out
 
 
-def audit_kloop(body, name=""):
+def audit_kloop(body):
     """-> None when the kernel has no stage statements, else (violations, n_stage_statements)."""
     blocks = [b for b in re.finditer(r";;#ASMSTART\n(.*?);;#ASMEND", body, re.S) if b.group(1).count("v_mfma") >= 8]
     if not blocks:
@@ -217,7 +213,7 @@ def audit_kloop(body, name=""):
             ins = line.strip().split()
             if ins and not ins[0].startswith(";") and (regs(line) & acc or ins[0].startswith("scratch_")):
                 viol.append("between stages: " + line.strip())
-    if "scratch_" in body and not SPILL_NOTED.search(name):
+    if "scratch_" in body:
         viol.append("kernel spills (scratch_ instructions)")
     return viol, len(blocks)
 
@@ -240,7 +236,7 @@ def main():
                     continue
                 n_asm += 1
                 viol, n_w, n_rd = audit_m0(body)
-                kl = audit_kloop(body, kname)
+                kl = audit_kloop(body)
                 if kl:
                     viol += kl[0]
                 tag = f"{kl[1]:3d} stage statements" if kl else "                    "
