@@ -13,9 +13,9 @@ probability-flow ODE, what run/demo.py's interpolation task decodes latents with
 runs as ``dposer_pf_sampler``: the drift's score term is halved and no noise is added or drawn.
 
 Every other registered pair -- the ``reverse_diffusion``, ``ancestral_sampling`` and ``none`` predictors, the ``langevin`` and ``ald``
-correctors -- runs as ``dposer_pc_sampler``: again one C call for the whole loop, per step [network + corrector update] x
-n_steps_each, network + predictor update, each update one elementwise kernel that also does the completion imputation and re-tiles x
-(``fused_pc_supported`` / ``fused_pc_sample``).  The discretisations read the SDE object's own ``discrete_betas`` /
+correctors -- runs as ``dposer_pc_sampler``: the same host loop in the library (the entries above are its Euler-Maruyama + 'none' case),
+per step [network + corrector update] x n_steps_each, network + predictor update, each update one elementwise kernel that also does
+the completion imputation and re-tiles x (``fused_pc_supported`` / ``fused_pc_sample``).  The discretisations read the SDE object's own ``discrete_betas`` /
 ``discrete_sigmas`` on the host; the entries of a step travel to the kernels by value.  What stays outside: Langevin under data
 parallelism (``fused_pc_langevin_sample``: three calls per step around the all-reduce of the two norm sums), and probability flow with
 a corrector, other models or SDEs: the generic loop below on top of the HIP score function.
@@ -23,6 +23,7 @@ a corrector, other models or SDEs: the generic loop below on top of the HIP scor
 import abc
 import ctypes as C
 import functools
+import types
 
 import numpy as np
 import torch
@@ -269,39 +270,38 @@ def fused_em_supported(sde, model, predictor, corrector, probability_flow, conti
             and isinstance(model, ScoreModelFC))
 
 
+def _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise):
+    """What the three ``fused_*`` runners set up alike: the engine and its buffers, the state clones, the host timesteps, the trajectory,
+    the SDE descriptor and the optional tensors as contiguous fp32.  The workspace is the caller's (its table rows differ)."""
+    _C.require_gpu(x, "sampler state")
+    p = types.SimpleNamespace(eng=model._engine(), flat=model.flat_params(), B=x.shape[0])
+    p.packed = p.eng.packed(p.flat, with_backward=False, force=not model.freeze_packed)
+    p.x = x.contiguous().float().clone()
+    p.x_mean = p.x.clone()
+    p.ts_host = timesteps.detach().to("cpu", torch.float32).contiguous()
+    p.traj = torch.empty((n_run // traj_stride,) + tuple(x.shape), dtype=torch.float32, device=x.device) if (traj_stride and n_run > 0) else None
+    p.desc = sde_lib.sde_desc(sde, continuous)
+    p.obs, p.msk, p.nz = (None if v is None else v.contiguous().float() for v in (observation, mask, noise))
+    return p
+
+
 def fused_em_sample(model, sde, x, timesteps, *, start_step=0, observation=None, mask=None, noise=None, seed=0,
                     traj_stride=0, continuous=True, probability_flow=False):
     """dposer_em_sampler (dposer_pf_sampler with ``probability_flow``).  x [B, D] initial state (consumed); returns
     (trajs or None, x, x_mean).  Under probability flow x == x_mean and ``noise`` keeps the stochastic layout: its predictor
     slots are not read."""
-    _C.require_gpu(x, "sampler state")
-    eng = model._engine()
-    flat = model.flat_params()
-    packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
-    B, D = x.shape
-    N = int(sde.N)
-    n_run = N - start_step
-    if B == 0:                      # nothing to sample: the reference's loop runs on empty tensors and returns them
-        x = x.contiguous().float().clone()
-        traj = torch.empty((max(n_run, 0) // traj_stride, 0, D), dtype=torch.float32, device=x.device) if traj_stride and n_run > 0 else None
-        return traj, x, x.clone()
+    n_run = int(sde.N) - start_step
+    p = _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise)
+    if p.B == 0:                    # nothing to sample: the reference's loop runs on empty tensors and returns them
+        return p.traj, p.x, p.x_mean
+    eng, B = p.eng, p.B
     ws = eng.workspace(B, _C.WS_SHARED_T, max(n_run, 1), x.device)
-    x = x.contiguous().float().clone()
-    x_mean = x.clone()
-    ts_host = timesteps.detach().to("cpu", torch.float32).contiguous()
-    traj = None
-    if traj_stride and n_run > 0:
-        traj = torch.empty((n_run // traj_stride, B, D), dtype=torch.float32, device=x.device)
-    desc = sde_lib.sde_desc(sde, continuous)
-    obs = None if observation is None else observation.contiguous().float()
-    msk = None if mask is None else mask.contiguous().float()
-    nz = None if noise is None else noise.contiguous().float()
     name = "dposer_pf_sampler" if probability_flow else "dposer_em_sampler"
-    _C.check(getattr(eng.lib, name)(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), _C.ptr(x), _C.ptr(x_mean),
-                                    C.c_void_p(ts_host.data_ptr()), int(start_step), _C.ptr(obs), _C.ptr(msk), _C.ptr(nz),
-                                    int(seed), _C.ptr(traj), int(traj_stride or 1), _C.ptr(eng.freq(x.device, model._fourier_W())),
+    _C.check(getattr(eng.lib, name)(eng.h, _C.ptr(p.flat), _C.ptr(p.packed), _C.ptr(ws), C.byref(p.desc), _C.ptr(p.x), _C.ptr(p.x_mean),
+                                    C.c_void_p(p.ts_host.data_ptr()), int(start_step), _C.ptr(p.obs), _C.ptr(p.msk), _C.ptr(p.nz),
+                                    int(seed), _C.ptr(p.traj), int(traj_stride or 1), _C.ptr(eng.freq(x.device, model._fourier_W())),
                                     _C.ptr(model.sigmas), B, _C.stream_ptr()), name)
-    return traj, x, x_mean
+    return p.traj, p.x, p.x_mean
 
 
 def fused_langevin_supported(sde, model, predictor, corrector, probability_flow, continuous):
@@ -319,21 +319,13 @@ def fused_pc_langevin_sample(model, sde, x, timesteps, *, snr, n_steps=1, start_
     step.  Nothing synchronises with the host inside the loop.
     ``noise`` [n_run, n_steps + (3 if completion else 1), B, D]: injected draws in the reference's order (tests)."""
     from ... import distributed as ddp
-    _C.require_gpu(x, "sampler state")
-    eng = model._engine()
-    flat = model.flat_params()
-    packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
-    B, D = x.shape
-    N = int(sde.N)
-    n_run = N - start_step
+    n_run = int(sde.N) - start_step
+    p = _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise)
+    # No early return for B == 0 here, unlike the one-call runners: this is the data-parallel path, and a rank with an empty shard
+    # still has to take part in every all-reduce below or its peers hang.  What B == 0 does is left as it always was.
+    eng, flat, packed, B, x, x_mean, ts_host, traj, desc, obs, msk, nz = (p.eng, p.flat, p.packed, p.B, p.x, p.x_mean, p.ts_host, p.traj, p.desc,
+                                                                          p.obs, p.msk, p.nz)
     ws = eng.workspace(B, _C.WS_SHARED_T, 1, x.device)
-    x = x.contiguous().float().clone()
-    x_mean = x.clone()
-    ts_host = timesteps.detach().to("cpu", torch.float32).contiguous()
-    desc = sde_lib.sde_desc(sde, continuous)
-    obs = None if observation is None else observation.contiguous().float()
-    msk = None if mask is None else mask.contiguous().float()
-    nz = None if noise is None else noise.contiguous().float()
     k_pred = 3 if obs is not None else 1
     dp = ddp.dp_active()
     global_batch = B
@@ -343,7 +335,6 @@ def fused_pc_langevin_sample(model, sde, x, timesteps, *, snr, n_steps=1, start_
         global_batch = int(cnt.item())
     norms = torch.empty(2, dtype=torch.float32, device=x.device)
     alphas = sde.alphas.detach().to("cpu") if hasattr(sde, "alphas") else None
-    traj = torch.empty((n_run // traj_stride, B, D), dtype=torch.float32, device=x.device) if (traj_stride and n_run > 0) else None
     freq, lib = eng.freq(x.device, model._fourier_W()), eng.lib
     for i in range(n_run):
         gi = start_step + i
@@ -421,39 +412,25 @@ def fused_pc_sample(model, sde, x, timesteps, *, predictor, corrector, snr=0.16,
     registered predictor / corrector class in ONE library call.  x [B, D] initial state (consumed); returns (trajs or None, x, x_mean).
     ``noise`` [n_run, (n_steps if a corrector) + (3 if completion else 1), B, D]: injected draws in the reference's order (corrector
     draws, impute-after-corrector, predictor z, impute-after-predictor); a slot the algorithm does not read is present and ignored."""
-    _C.require_gpu(x, "sampler state")
-    eng = model._engine()
-    flat = model.flat_params()
-    packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
-    B, D = x.shape
     N = int(sde.N)
     n_run = N - start_step if (run_steps < 0 or run_steps > N - start_step) else int(run_steps)
-    x = x.contiguous().float().clone()
-    if B == 0:                      # nothing to sample: the reference's loop runs on empty tensors and returns them
-        traj = torch.empty((max(n_run, 0) // traj_stride, 0, D), dtype=torch.float32, device=x.device) if traj_stride and n_run > 0 else None
-        return traj, x, x.clone()
+    p = _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise)
+    if p.B == 0:                    # nothing to sample: the reference's loop runs on empty tensors and returns them
+        return p.traj, p.x, p.x_mean
+    eng, B = p.eng, p.B
     ws = eng.workspace(B, _C.WS_SHARED_T, max(n_run, 1), x.device)
-    x_mean = x.clone()
-    ts_host = timesteps.detach().to("cpu", torch.float32).contiguous()
-    traj = None
-    if traj_stride and n_run > 0:
-        traj = torch.empty((n_run // traj_stride, B, D), dtype=torch.float32, device=x.device)
-    desc = sde_lib.sde_desc(sde, continuous)
     pc = _C.PcDesc(_PC_PRED_KINDS[predictor], _PC_CORR_KINDS[corrector], int(n_steps), int(bool(probability_flow)), float(snr), 1.0 / B)
     table = _discrete_table(sde) if _pc_reads_table(sde, pc.predictor, pc.corrector) else None
     if table is None and _pc_reads_table(sde, pc.predictor, pc.corrector):
         raise ValueError("the SDE's discrete table no longer has sde.N entries: this predictor / corrector pair cannot run on it")
     norms = torch.empty(2, dtype=torch.float32, device=x.device) if pc.corrector == _C.PC_CORR_LANGEVIN else None
-    obs = None if observation is None else observation.contiguous().float()
-    msk = None if mask is None else mask.contiguous().float()
-    nz = None if noise is None else noise.contiguous().float()
-    _C.check(eng.lib.dposer_pc_sampler(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), C.byref(pc), _C.ptr(x), _C.ptr(x_mean),
-                                       C.c_void_p(ts_host.data_ptr()), int(start_step), int(run_steps), _C.ptr(obs), _C.ptr(msk), _C.ptr(nz),
-                                       int(seed), _C.ptr(traj), int(traj_stride or 1),
+    _C.check(eng.lib.dposer_pc_sampler(eng.h, _C.ptr(p.flat), _C.ptr(p.packed), _C.ptr(ws), C.byref(p.desc), C.byref(pc), _C.ptr(p.x),
+                                       _C.ptr(p.x_mean), C.c_void_p(p.ts_host.data_ptr()), int(start_step), int(run_steps), _C.ptr(p.obs),
+                                       _C.ptr(p.msk), _C.ptr(p.nz), int(seed), _C.ptr(p.traj), int(traj_stride or 1),
                                        C.c_void_p(table.data_ptr()) if table is not None else None, _C.ptr(norms),
                                        _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B, _C.stream_ptr()),
              "dposer_pc_sampler")
-    return traj, x, x_mean
+    return p.traj, p.x, p.x_mean
 
 
 def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_steps=1, probability_flow=False,
@@ -465,10 +442,13 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
     arguments: ``traj_stride`` (default 1 = every step as the reference; 0 = keep no trajectory --
     at B = 65536, N = 1000 the full tensor is 16.5 GB), ``noise`` (injected draws for tests),
     ``seed`` (Philox key of the in-kernel noise)."""
-    predictor_update_fn = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor,
-                                            probability_flow=probability_flow, continuous=continuous)
-    corrector_update_fn = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous,
-                                            snr=snr, n_steps=n_steps)
+    def predictor_update_fn(x, t, observation, mask, model):          # (the module-level names: looked up at each call)
+        return shared_predictor_update_fn(x, t, observation, mask, sde=sde, model=model, predictor=predictor,
+                                          probability_flow=probability_flow, continuous=continuous)
+
+    def corrector_update_fn(x, t, observation, mask, model):
+        return shared_corrector_update_fn(x, t, observation, mask, sde=sde, model=model, corrector=corrector, continuous=continuous,
+                                          snr=snr, n_steps=n_steps)
 
     def with_imputation(update_fn):
         def fn(x, vec_t, observation, mask, model, args):
@@ -493,46 +473,24 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
             timesteps = torch.linspace(sde.T, eps, sde.N, device=device)          # sampling.py:449
             start_t = start_step if (args is not None and args.task in ["denoise"]) else 0
             completion = args is not None and args.task in ["completion"]
-            if fused_em_supported(sde, model, predictor, corrector, probability_flow, continuous):
+            pair = (sde, model, predictor, corrector, probability_flow, continuous)
+            runner = None                              # the one-call paths, in this order; each name is looked up at this call
+            if fused_em_supported(*pair):
+                runner = functools.partial(fused_em_sample, probability_flow=probability_flow)
+            elif fused_pc_supported(*pair):
+                runner = functools.partial(fused_pc_sample, predictor=predictor, corrector=corrector, snr=snr, n_steps=n_steps,
+                                           probability_flow=probability_flow)
+            elif fused_langevin_supported(*pair):
+                runner = functools.partial(fused_pc_langevin_sample, snr=snr, n_steps=n_steps)
+            if runner is not None:
                 call_count[0] += 1
                 if seed is None:
                     seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
                 was_training = model.training
                 model.eval()                                                       # utils.py:117-119
-                trajs, x, x_mean = fused_em_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), start_step=start_t,
-                                                   observation=observation if completion else None,
-                                                   mask=mask if completion else None, noise=noise, seed=seed,
-                                                   traj_stride=traj_stride, continuous=continuous,
-                                                   probability_flow=probability_flow)
-                model.train(was_training)
-                if trajs is None:
-                    trajs = x.new_empty((0,) + tuple(x.shape))
-                return trajs, (x_mean if denoise else x)
-            if fused_pc_supported(sde, model, predictor, corrector, probability_flow, continuous):
-                call_count[0] += 1
-                if seed is None:
-                    seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
-                was_training = model.training
-                model.eval()
-                trajs, x, x_mean = fused_pc_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), predictor=predictor,
-                                                   corrector=corrector, snr=snr, n_steps=n_steps, probability_flow=probability_flow,
-                                                   start_step=start_t, observation=observation if completion else None,
-                                                   mask=mask if completion else None, noise=noise, seed=seed,
-                                                   traj_stride=traj_stride, continuous=continuous)
-                model.train(was_training)
-                if trajs is None:
-                    trajs = x.new_empty((0,) + tuple(x.shape))
-                return trajs, (x_mean if denoise else x)
-            if fused_langevin_supported(sde, model, predictor, corrector, probability_flow, continuous):
-                call_count[0] += 1
-                if seed is None:
-                    seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
-                was_training = model.training
-                model.eval()
-                trajs, x, x_mean = fused_pc_langevin_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), snr=snr, n_steps=n_steps,
-                                                            start_step=start_t, observation=observation if completion else None,
-                                                            mask=mask if completion else None, noise=noise, seed=seed,
-                                                            traj_stride=traj_stride, continuous=continuous)
+                trajs, x, x_mean = runner(model, sde, x, torch.linspace(sde.T, eps, sde.N), start_step=start_t,
+                                          observation=observation if completion else None, mask=mask if completion else None,
+                                          noise=noise, seed=seed, traj_stride=traj_stride, continuous=continuous)
                 model.train(was_training)
                 if trajs is None:
                     trajs = x.new_empty((0,) + tuple(x.shape))

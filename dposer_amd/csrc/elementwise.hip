@@ -291,11 +291,24 @@ hipError_t launch_out_model(const OutModelArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-struct EmDev {
-    EmUpdateArgs a;
+// a kernel's arguments together with the SDE's per-launch constants
+template <typename A> struct WithSde {
+    A a;
     SdeDev sde;
 };
-template <typename T> __global__ void __launch_bounds__(256) k_em_update(EmDev d) {
+// launches one of the kernels that walk the Bpad x (Dpad / 4) quads of the FT-tiled state: fp32 / bf16 storage by a.f32
+template <typename A> static hipError_t launch_quads(void (*k32)(WithSde<A>), void (*k16)(WithSde<A>), const A& a, const SdeDev& sde, hipStream_t st) {
+    const WithSde<A> d = {a, sde};
+    hipLaunchKernelGGL(a.f32 ? k32 : k16, dim3(grid_for(a.Bpad * (a.Dpad >> 2))), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+// the divisor of the model output at a launch's shared label (model.py:189-194)
+template <typename A> __device__ __forceinline__ float launch_usig(const A& a, float label) {
+    return a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, label, a.scale_by_sigma == 2) : 1.0f;
+}
+// completion imputation (sampling.py:416-420): x (1 - mask) + (mean + z std) mask, mean = mc * observation
+__device__ __forceinline__ float impute(float x, float m, float obs, float mc, float z, float sd) { return x * (1.0f - m) + (mc * obs + z * sd) * m; }
+template <typename T> __global__ void __launch_bounds__(256) k_em_update(WithSde<EmUpdateArgs> d) {
     const EmUpdateArgs& a = d.a;
     const int qx = a.Dpad >> 2;
     const int QD = (a.D + 3) >> 2;
@@ -304,7 +317,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_em_update(EmDev d
     const float t = a.t;
     const SdeAt at = sde_at(d.sde, t);
     const float mc = at.mc, sd = at.sd, beta = at.beta, g = at.g, label = at.label;
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, label);
     float mcn = 0.f, sdn = 0.f;
     if (a.t_next >= 0.f) { const SdeAt an = sde_at(d.sde, a.t_next); mcn = an.mc; sdn = an.sd; }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -338,16 +351,12 @@ template <typename T> __global__ void __launch_bounds__(256) k_em_update(EmDev d
                     }
                     a.x_mean[o] = x_mean;
                     if (a.obs) {                                                   // sampling.py:416-420 (after predictor)
-                        const float m = a.mask[o];
-                        const float nz = a.z_impB ? a.z_impB[o] : zb[r];
-                        x = x * (1.0f - m) + (mc * a.obs[o] + nz * sd) * m;
+                        x = impute(x, a.mask[o], a.obs[o], mc, a.z_impB ? a.z_impB[o] : zb[r], sd);
                     }
                     if (a.traj) a.traj[o] = x;                                     // sampling.py:461
                 }
                 if (a.obs && a.t_next >= 0.f) {                                    // imputation ahead of the next predictor call
-                    const float m = a.mask[o];
-                    const float nz = a.z_impA ? a.z_impA[o] : za[r];
-                    x = x * (1.0f - m) + (mcn * a.obs[o] + nz * sdn) * m;
+                    x = impute(x, a.mask[o], a.obs[o], mcn, a.z_impA ? a.z_impA[o] : za[r], sdn);
                 }
                 a.x[o] = x;
                 xn[r] = x;
@@ -381,15 +390,7 @@ hipError_t launch_ft_to_rows(const float* a_ft, float* a, const float* b_ft, flo
     hipLaunchKernelGGL(k_ft_to_rows, dim3(grid_for(B * (Dpad >> 2))), dim3(256), 0, st, a_ft, a, b_ft, b, B, D, Dpad);
     return hipGetLastError();
 }
-hipError_t launch_em_update(const EmUpdateArgs& a, hipStream_t st) {
-    EmDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
-    const int64_t total = a.Bpad * (a.Dpad >> 2);
-    if (a.f32) hipLaunchKernelGGL(k_em_update<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(k_em_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    return hipGetLastError();
-}
+hipError_t launch_em_update(const EmUpdateArgs& a, hipStream_t st) { return launch_quads(k_em_update<float>, k_em_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
 
 // block-wide sum -> one partial per block (deterministic)
 __device__ __forceinline__ float block_sum_256(float v) {
@@ -403,11 +404,7 @@ __device__ __forceinline__ float block_sum_256(float v) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-struct PerturbDev {
-    PerturbSharedArgs a;
-    SdeDev sde;
-};
-template <typename T> __global__ void __launch_bounds__(256) k_perturb_shared(PerturbDev d) {
+template <typename T> __global__ void __launch_bounds__(256) k_perturb_shared(WithSde<PerturbSharedArgs> d) {
     const PerturbSharedArgs& a = d.a;
     const int qx = a.Dpad >> 2;
     const int QD = (a.D + 3) >> 2;
@@ -433,28 +430,16 @@ template <typename T> __global__ void __launch_bounds__(256) k_perturb_shared(Pe
         *reinterpret_cast<f32x4*>(a.xt + s * a.Dpad + c) = v;
     }
 }
-hipError_t launch_perturb_shared(const PerturbSharedArgs& a, hipStream_t st) {
-    PerturbDev d;
-    d.a = a;
-    d.sde = make_sde_dev(a.sde);
-    const int64_t total = a.Bpad * (a.Dpad >> 2);
-    if (a.f32) hipLaunchKernelGGL(k_perturb_shared<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(k_perturb_shared<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    return hipGetLastError();
-}
+hipError_t launch_perturb_shared(const PerturbSharedArgs& a, hipStream_t st) { return launch_quads(k_perturb_shared<float>, k_perturb_shared<__bf16>, a, make_sde_dev(a.sde), st); }
 
-struct DenoiseDev {
-    DenoiseArgs a;
-    SdeDev sde;
-};
-__global__ void __launch_bounds__(256) k_denoise(DenoiseDev d) {
+__global__ void __launch_bounds__(256) k_denoise(WithSde<DenoiseArgs> d) {
     const DenoiseArgs& a = d.a;
     const float t = a.t;
     const SdeAt at = sde_at(d.sde, t);
     const float alpha = at.mc, sigma = at.sd;                         // return_alpha_sigma, sde_lib.py:227-231 (VE: 1, sigma(t), :289-292)
     const float sigma2 = sigma * sigma;
     const float label = at.label;
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, label);
     const float snr = alpha / sqrtf(sigma2);                          // completion.py:108
     const float w = a.weighted ? 0.5f * sqrtf(1.0f + snr) : 0.5f;     // completion.py:143-146
     float acc = 0.f;
@@ -474,9 +459,7 @@ __global__ void __launch_bounds__(256) k_denoise(DenoiseDev d) {
     if (threadIdx.x == 0) a.loss_part[blockIdx.x] = tot * a.inv_n;
 }
 hipError_t launch_denoise(const DenoiseArgs& a, int* nblocks, hipStream_t st) {
-    DenoiseDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
+    const WithSde<DenoiseArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
     const int g = grid_for(a.B * a.D, 256, 1024);
     *nblocks = g;
     hipLaunchKernelGGL(k_denoise, dim3(g), dim3(256), 0, st, d);
@@ -489,18 +472,14 @@ hipError_t launch_denoise(const DenoiseArgs& a, int* nblocks, hipStream_t st) {
 // and written as fp32 rows (xt) and re-tiled for the next GEMM (xin; padded rows / columns are zeros, as k_perturb_shared writes them).  The
 // LAST step writes no state: the same pass forms x0_hat, the gradient 2 w (x0 - x0_hat) inv_n and the block partials of the loss
 // (completion.py:142-147; w from the SNR alpha / sigma at time_traj[0], :127-128).
-struct DdimDev {
-    DdimStepArgs a;
-    SdeDev sde;
-};
-template <typename T> __global__ void __launch_bounds__(256) k_ddim_step(DdimDev d) {
+template <typename T> __global__ void __launch_bounds__(256) k_ddim_step(WithSde<DdimStepArgs> d) {
     const DdimStepArgs& a = d.a;
     const int qx = a.Dpad >> 2;
     const SdeAt at = sde_at(d.sde, a.t);
     const SdeAt ab = sde_at(d.sde, a.t_next);
     const float a_c = at.mc, s_c = at.sd, s_b = ab.sd;               // return_alpha_sigma, sde_lib.py:177-181 / :227-231 / :289-292
     const float ratio = ab.mc / a_c;
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     float w = 0.5f;
     if (a.last && a.weighted) {
         const SdeAt a0 = sde_at(d.sde, a.t0);
@@ -543,9 +522,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_ddim_step(DdimDev
     }
 }
 hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st) {
-    DdimDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
+    const WithSde<DdimStepArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
     const int g = grid_for(a.Bpad * (a.Dpad >> 2), 256, a.last ? 1024 : 8192);      // (last step: one partial per block, as k_denoise)
     *nblocks = g;
     if (a.f32) hipLaunchKernelGGL(k_ddim_step<float>, dim3(g), dim3(256), 0, st, d);
@@ -557,16 +534,12 @@ hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st)
 //   eps_pred = -score * std;   weight = sqrt(sigma^2) / alpha;   guidance = mean_b(weight * <(eps_pred - z).detach(), x_0>)
 // and its gradient weight (eps_pred - z) / B w.r.t. x_0.  z is the perturbation's: the injected array, or the Philox draws of
 // k_perturb_shared regenerated from the same counters.  One quad per thread, block partials in a fixed order: no float atomics.
-struct RedDiffDev {
-    RedDiffArgs a;
-    SdeDev sde;
-};
-__global__ void __launch_bounds__(256) k_red_diff(RedDiffDev d) {
+__global__ void __launch_bounds__(256) k_red_diff(WithSde<RedDiffArgs> d) {
     const RedDiffArgs& a = d.a;
     const int QD = (a.D + 3) >> 2;
     const SdeAt at = sde_at(d.sde, a.t);
     const float alpha = at.mc, sigma = at.sd;                         // return_alpha_sigma; marginal_prob's std is the same number
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     const float weight = sqrtf(sigma * sigma) / alpha;                // motion_denoising.py:151-152
     float acc = 0.f;
     const int64_t total = a.B * QD;
@@ -595,9 +568,7 @@ __global__ void __launch_bounds__(256) k_red_diff(RedDiffDev d) {
     if (threadIdx.x == 0) a.loss_part[blockIdx.x] = (weight * tot) * a.inv_batch;
 }
 hipError_t launch_red_diff(const RedDiffArgs& a, int* nblocks, hipStream_t st) {
-    RedDiffDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
+    const WithSde<RedDiffArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
     const int g = grid_for(a.B * ((a.D + 3) >> 2), 256, 1024);
     *nblocks = g;
     hipLaunchKernelGGL(k_red_diff, dim3(g), dim3(256), 0, st, d);
@@ -608,16 +579,12 @@ hipError_t launch_red_diff(const RedDiffArgs& a, int* nblocks, hipStream_t st) {
 //   w_prior * mean(w (x - x0_hat)^2) + w_data * MSE(x * mask, obs * mask)                (completion.py:131-149,195-201)
 // w.r.t. x (x0_hat is detached in the reference), and torch.optim.Adam's update of x with per-element moments -- one pass
 // over seven [B, D] streams instead of ~10 torch kernels.
-struct CompletionDev {
-    CompletionUpdateArgs a;
-    SdeDev sde;
-};
-__global__ void __launch_bounds__(256) k_completion_update(CompletionDev d) {
+__global__ void __launch_bounds__(256) k_completion_update(WithSde<CompletionUpdateArgs> d) {
     const CompletionUpdateArgs& a = d.a;
     const SdeAt at = sde_at(d.sde, a.t);
     const float alpha = at.mc, sigma = at.sd;                         // return_alpha_sigma, sde_lib.py:227-231
     const float sigma2 = sigma * sigma;
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     const float snr = alpha / sqrtf(sigma2);                          // completion.py:108
     const float w = a.weighted ? 0.5f * sqrtf(1.0f + snr) : 0.5f;     // completion.py:143-146
     const int64_t total = a.B * a.D;
@@ -643,9 +610,7 @@ __global__ void __launch_bounds__(256) k_completion_update(CompletionDev d) {
     }
 }
 hipError_t launch_completion_update(const CompletionUpdateArgs& a, hipStream_t st) {
-    CompletionDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
+    const WithSde<CompletionUpdateArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
     hipLaunchKernelGGL(k_completion_update, dim3(grid_for(a.B * a.D, 256, 2048)), dim3(256), 0, st, d);
     return hipGetLastError();
 }
@@ -656,19 +621,15 @@ hipError_t launch_completion_update(const CompletionUpdateArgs& a, hipStream_t s
 //   x_mean = x + step * grad;   x = x_mean + sqrt(2 step) * noise
 // Two passes around the grid-wide (and, under data parallelism, cross-rank) mean: norms -> [all-reduce of two scalars] -> update.
 // Both recompute score and noise from the same inputs / Philox counters, so nothing but the two sums travels between them.
-struct LangevinDev {
-    LangevinArgs a;
-    SdeDev sde;
-};
-__device__ __forceinline__ float langevin_score(const LangevinDev& d, float res, float usig, float sd) {
-    return sde_score(d.sde, res / usig, sd);                          // model.py:194, utils.py:155,162
+__device__ __forceinline__ float langevin_score(const SdeDev& sde, float res, float usig, float sd) {
+    return sde_score(sde, res / usig, sd);                          // model.py:194, utils.py:155,162
 }
-__global__ void __launch_bounds__(256) k_langevin_norms(LangevinDev d) {
+__global__ void __launch_bounds__(256) k_langevin_norms(WithSde<LangevinArgs> d) {
     const LangevinArgs& a = d.a;
     const int QD = (a.D + 3) >> 2;
     const SdeAt at = sde_at(d.sde, a.t);
     const float sd = at.sd_score;      // (the score's std: utils.py:155 / :160)
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     float gsum = 0.f, nsum = 0.f;
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < a.B; s += (int64_t)gridDim.x * blockDim.x) {
         float g2 = 0.f, n2 = 0.f;
@@ -679,7 +640,7 @@ __global__ void __launch_bounds__(256) k_langevin_norms(LangevinDev d) {
             for (int r = 0; r < 4; ++r) {
                 const int c = q * 4 + r;
                 if (c >= a.D) continue;
-                const float g = langevin_score(d, a.res[s * a.Cp + c], usig, sd);
+                const float g = langevin_score(d.sde, a.res[s * a.Cp + c], usig, sd);
                 const float n = a.noise ? a.noise[s * a.D + c] : z[r];
                 g2 += g * g;
                 n2 += n * n;
@@ -694,9 +655,7 @@ __global__ void __launch_bounds__(256) k_langevin_norms(LangevinDev d) {
     if (threadIdx.x == 0) { a.part[blockIdx.x] = gt; a.part[gridDim.x + blockIdx.x] = nt; }
 }
 hipError_t launch_langevin_norms(const LangevinArgs& a, int* nblocks, hipStream_t st) {
-    LangevinDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
+    const WithSde<LangevinArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
     const int g = grid_for(a.B, 256, 1024);
     *nblocks = g;
     hipLaunchKernelGGL(k_langevin_norms, dim3(g), dim3(256), 0, st, d);
@@ -712,13 +671,13 @@ hipError_t launch_sum_partials2(const float* part, int n, float* out2, hipStream
     hipLaunchKernelGGL(k_sum_partials2, dim3(2), dim3(256), 0, st, part, n, out2);
     return hipGetLastError();
 }
-template <typename T> __global__ void __launch_bounds__(256) k_langevin_update(LangevinDev d) {
+template <typename T> __global__ void __launch_bounds__(256) k_langevin_update(WithSde<LangevinArgs> d) {
     const LangevinArgs& a = d.a;
     const int qx = a.Dpad >> 2;
     const int QD = (a.D + 3) >> 2;
     const SdeAt at = sde_at(d.sde, a.t);
     const float sd = at.sd_score;      // (the score's std: utils.py:155 / :160)
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     const float grad_norm = a.norm_sums[0] * a.inv_global_batch, noise_norm = a.norm_sums[1] * a.inv_global_batch;   // .mean()
     const float r0 = a.snr * noise_norm / grad_norm;
     const float step = ((r0 * r0) * 2.0f) * a.alpha;                  // sampling.py:298
@@ -736,7 +695,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_langevin_update(L
             for (int r = 0; r < 4; ++r) {
                 if (c + r >= a.D) continue;
                 const int64_t o = s * a.D + c + r;
-                const float g = langevin_score(d, a.res[s * a.Cp + c + r], usig, sd);
+                const float g = langevin_score(d.sde, a.res[s * a.Cp + c + r], usig, sd);
                 const float n = a.noise ? a.noise[o] : z[r];
                 const float xm = a.x[o] + step * g;                   // :299
                 const float x = xm + nscale * n;                      // :300
@@ -748,29 +707,17 @@ template <typename T> __global__ void __launch_bounds__(256) k_langevin_update(L
         if (a.xin) store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
     }
 }
-hipError_t launch_langevin_update(const LangevinArgs& a, hipStream_t st) {
-    LangevinDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
-    const int64_t total = a.Bpad * (a.Dpad >> 2);
-    if (a.f32) hipLaunchKernelGGL(k_langevin_update<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(k_langevin_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    return hipGetLastError();
-}
+hipError_t launch_langevin_update(const LangevinArgs& a, hipStream_t st) { return launch_quads(k_langevin_update<float>, k_langevin_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
 // ---- predictors other than Euler-Maruyama (sampling.py:210-270) + imputation (:416-420): k_em_update's shape -----------------
 // The predictor kind and the SDE kind are uniform per launch (kernel arguments): the branches in pc_pred_step do not diverge.
-struct PcPredDev {
-    PcPredArgs a;
-    SdeDev sde;
-};
-template <typename T> __global__ void __launch_bounds__(256) k_pc_pred_update(PcPredDev d) {
+template <typename T> __global__ void __launch_bounds__(256) k_pc_pred_update(WithSde<PcPredArgs> d) {
     const PcPredArgs& a = d.a;
     const int qx = a.Dpad >> 2;
     const int QD = (a.D + 3) >> 2;
     const int64_t total = a.Bpad * qx;
     const SdeAt at = sde_at(d.sde, a.t);
     const float mc = at.mc, sd = at.sd;
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     const PcPredScal ks = pc_pred_scalars(d.sde, at, a.tab, a.pred);
     const bool score_read = a.pred != DPOSER_PC_PRED_NONE;
     const bool draws = score_read && !a.pf;
@@ -798,15 +745,11 @@ template <typename T> __global__ void __launch_bounds__(256) k_pc_pred_update(Pc
                 x = pc_pred_step(d.sde, a.tab, ks, a.pred, a.pf, x, score, z, &x_mean);
                 a.x_mean[o] = x_mean;
                 if (a.obs) {                                                   // sampling.py:416-420 (after predictor)
-                    const float m = a.mask[o];
-                    const float nz = a.z_impB ? a.z_impB[o] : zb[r];
-                    x = x * (1.0f - m) + (mc * a.obs[o] + nz * sd) * m;
+                    x = impute(x, a.mask[o], a.obs[o], mc, a.z_impB ? a.z_impB[o] : zb[r], sd);
                 }
                 if (a.traj) a.traj[o] = x;                                     // sampling.py:461
                 if (a.obs && a.t_next >= 0.f) {                                // corrector 'none': imputation ahead of the next predictor call
-                    const float m = a.mask[o];
-                    const float nz = a.z_impA ? a.z_impA[o] : za[r];
-                    x = x * (1.0f - m) + (mcn * a.obs[o] + nz * sdn) * m;
+                    x = impute(x, a.mask[o], a.obs[o], mcn, a.z_impA ? a.z_impA[o] : za[r], sdn);
                 }
                 a.x[o] = x;
                 xn[r] = x;
@@ -815,26 +758,14 @@ template <typename T> __global__ void __launch_bounds__(256) k_pc_pred_update(Pc
         store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
     }
 }
-hipError_t launch_pc_pred_update(const PcPredArgs& a, hipStream_t st) {
-    PcPredDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
-    const int64_t total = a.Bpad * (a.Dpad >> 2);
-    if (a.f32) hipLaunchKernelGGL(k_pc_pred_update<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(k_pc_pred_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    return hipGetLastError();
-}
+hipError_t launch_pc_pred_update(const PcPredArgs& a, hipStream_t st) { return launch_quads(k_pc_pred_update<float>, k_pc_pred_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
 // ---- annealed Langevin dynamics (sampling.py:319-339): no batch coupling, one pass; k_langevin_update's shape -------------------
-struct AldDev {
-    AldArgs a;
-    SdeDev sde;
-};
-template <typename T> __global__ void __launch_bounds__(256) k_ald_update(AldDev d) {
+template <typename T> __global__ void __launch_bounds__(256) k_ald_update(WithSde<AldArgs> d) {
     const AldArgs& a = d.a;
     const int qx = a.Dpad >> 2;
     const int QD = (a.D + 3) >> 2;
     const SdeAt at = sde_at(d.sde, a.t);
-    const float usig = a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, at.label, a.scale_by_sigma == 2) : 1.0f;
+    const float usig = launch_usig(a, at.label);
     const float step = pc_ald_step_size(a.snr, at.sd, a.alpha);      // std of marginal_prob (:330), not the score's
     const float nscale = sqrtf(step * 2.0f);                          // :337
     const int64_t total = a.Bpad * qx;
@@ -857,9 +788,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_ald_update(AldDev
                 float x = xm + n * nscale;                            // :337
                 if (a.x_mean) a.x_mean[o] = xm;
                 if (a.obs) {                                          // sampling.py:416-420 (after corrector)
-                    const float m = a.mask[o];
-                    const float nz = a.z_imp ? a.z_imp[o] : zi[r];
-                    x = x * (1.0f - m) + (at.mc * a.obs[o] + nz * at.sd) * m;
+                    x = impute(x, a.mask[o], a.obs[o], at.mc, a.z_imp ? a.z_imp[o] : zi[r], at.sd);
                 }
                 a.x[o] = x;
                 xn[r] = x;
@@ -868,15 +797,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_ald_update(AldDev
         store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
     }
 }
-hipError_t launch_ald_update(const AldArgs& a, hipStream_t st) {
-    AldDev d;
-    d.a = a;
-    d.sde = make_sde_dev_at(a.sde, a.t);
-    const int64_t total = a.Bpad * (a.Dpad >> 2);
-    if (a.f32) hipLaunchKernelGGL(k_ald_update<float>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(k_ald_update<__bf16>, dim3(grid_for(total)), dim3(256), 0, st, d);
-    return hipGetLastError();
-}
+hipError_t launch_ald_update(const AldArgs& a, hipStream_t st) { return launch_quads(k_ald_update<float>, k_ald_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
 // row-major [B][D] fp32 -> FT [Bpad][Dpad] network input (zero padded)
 template <typename T> __global__ void __launch_bounds__(256) k_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, int D, int Dpad) {
     const int qx = Dpad >> 2;
@@ -899,14 +820,10 @@ hipError_t launch_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, 
     return hipGetLastError();
 }
 
-struct DsmDev {
-    DsmArgs a;
-    SdeDev sde;
-};
 // One thread keeps ONE channel quad q for all of its samples (thread t: q = t % qc, sample lane t / qc; 256 / qc sample lanes per block),
 // so that the column sums of dres -- the gradient of post_dense's bias, a k_colsum launch of its own before -- are per-thread running sums:
 // each block leaves one partial row [Cp] (fixed order: sample lanes in turn), the last reduction of the step adds the rows.
-template <typename T> __global__ void __launch_bounds__(256) k_dsm(DsmDev d) {
+template <typename T> __global__ void __launch_bounds__(256) k_dsm(WithSde<DsmArgs> d) {
     __shared__ float cs[256][4];
     const DsmArgs& a = d.a;
     const int qc = a.Cp >> 2;
@@ -955,9 +872,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_dsm(DsmDev d) {
     }
 }
 hipError_t launch_dsm(const DsmArgs& a, int* nblocks, hipStream_t st) {
-    DsmDev d;
-    d.a = a;
-    d.sde = make_sde_dev(a.sde);
+    const WithSde<DsmArgs> d = {a, make_sde_dev(a.sde)};
     const int lanes = 256 / (a.Cp >> 2);
     int64_t g = (a.Bpad + lanes - 1) / lanes;
     g = g < 1 ? 1 : (g > 1024 ? 1024 : g);

@@ -82,27 +82,34 @@ struct OutModelArgs {      // ScoreModelFC.forward tail: res / used_sigmas   (mo
 };
 hipError_t launch_out_model(const OutModelArgs& a, hipStream_t st);
 
-struct EmUpdateArgs {      // EulerMaruyamaPredictor.update_fn + imputation (sampling.py:182-188, 416-420)
-    const float* res;      // [Bpad][Cp] post_dense output of this step (null: no predictor step, only impute A + pack)
+// What the four update kernels of the samplers share (scorefc.hip: update_common fills it from the handle, the workspace and the call).
+// t and step sit with the pointers, no padding anywhere: the blocks keep their sizes, and each kernel's first batch of scalar loads
+// touches every cache line of its argument block (with t behind `seed` k_langevin_norms took 0.6 us longer per launch).
+struct UpdateCommon {
+    const float* res;      // [Bpad][Cp] post_dense output at x
     float* x;              // [B][D] state, updated in place
     float* x_mean;         // [B][D]
-    void* xin;             // FT [Bpad][Dpad]: next step's network input
-    float* traj;           // [B][D] slot for this step or null
-    float* x_ft;           // optional: the new state again as fp32 FT [Bpad][Dpad] (start of the fused sampler fast path)
+    void* xin;             // FT [Bpad][Dpad]: the new state as the next network input
     const float* sigmas;
-    const float* obs;      // completion: observation [B][D] or null
-    const float* mask;     // completion: mask [B][D]
-    const float* z_pred;   // injected predictor noise [B][D] or null (-> Philox); not read under probability flow
-    const float* z_impB;   // injected imputation noise after the predictor, or null
-    const float* z_impA;   // injected imputation noise before the NEXT predictor step, or null
-    float t, t_next;       // current / next timestep (t_next < 0: last step, no look-ahead imputation)
+    float t;               // the launch's shared time
+    uint32_t step;
     int64_t B, Bpad;
     int D, Dpad, Cp, num_scales;
     int f32;
     int scale_by_sigma;
     SdeCfg sde;
     uint64_t seed;
-    uint32_t step;
+};
+struct EmUpdateArgs : UpdateCommon {   // EulerMaruyamaPredictor.update_fn + imputation (sampling.py:182-188, 416-420)
+    // res == null: no predictor step, only impute A + pack
+    const float* obs;      // completion: observation [B][D] or null
+    const float* mask;     // completion: mask [B][D]
+    float* traj;           // [B][D] slot for this step or null
+    float* x_ft;           // optional: the new state again as fp32 FT [Bpad][Dpad] (start of the fused sampler fast path)
+    const float* z_pred;   // injected predictor noise [B][D] or null (-> Philox); not read under probability flow
+    const float* z_impB;   // injected imputation noise after the predictor, or null
+    const float* z_impA;   // injected imputation noise before the NEXT predictor step, or null
+    float t_next;          // next timestep (< 0: last step, no look-ahead imputation)
     int pf;                // probability-flow ODE step: drift factor 0.5, no diffusion, no predictor draw (sde_lib.py:102-104)
 };
 hipError_t launch_em_update(const EmUpdateArgs& a, hipStream_t st);
@@ -198,21 +205,12 @@ struct CompletionUpdateArgs {   // one optimisation step of DPoserComp.optimize 
 };
 hipError_t launch_completion_update(const CompletionUpdateArgs& a, hipStream_t st);
 
-struct LangevinArgs {           // LangevinCorrector.update_fn (sampling.py:282-302) around one network evaluation at a shared t
-    const float* res;      // [Bpad][Cp] model output at x
+struct LangevinArgs : UpdateCommon {   // LangevinCorrector.update_fn (sampling.py:282-302) around one network evaluation at a shared t
+    // x_mean: out (update phase); xin: written by the update phase, or null
     const float* noise;    // injected noise [B][D] or null (-> Philox STREAM_LANGEVIN)
-    const float* sigmas;
-    float* x;              // [B][D] state (update phase: in/out)
-    float* x_mean;         // [B][D] out (update phase)
-    void* xin;             // FT [Bpad][Dpad]: the updated state packed as the next network input (update phase) or null
     float* part;           // norms phase: per-block partial sums, [2][nblocks]
     const float* norm_sums;// update phase: [2] = sum_b ||grad_b||, sum_b ||noise_b|| over the GLOBAL batch
-    float t, alpha, snr, inv_global_batch;
-    int64_t B, Bpad;
-    int D, Dpad, Cp, num_scales, scale_by_sigma, f32;
-    SdeCfg sde;
-    uint64_t seed;
-    uint32_t step;
+    float alpha, snr, inv_global_batch;
 };
 hipError_t launch_langevin_norms(const LangevinArgs& a, int* nblocks, hipStream_t st);
 hipError_t launch_sum_partials2(const float* part, int n, float* out2, hipStream_t st);   // out2[k] = sum part[k*n .. k*n+n)
@@ -220,45 +218,28 @@ hipError_t launch_langevin_update(const LangevinArgs& a, hipStream_t st);
 hipError_t launch_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, int D, int Dpad, int f32, hipStream_t st);
 
 // ---- one-call predictor-corrector sampler: the predictors that are not Euler-Maruyama, and annealed Langevin dynamics ----
-struct PcPredArgs {        // ReverseDiffusion / AncestralSampling / None predictor + imputation (sampling.py:210-270, 416-420)
-    const float* res;      // [Bpad][Cp] post_dense output at x (not read by the 'none' predictor; may be null then)
-    float* x;              // [B][D] state, updated in place
-    float* x_mean;         // [B][D]
-    void* xin;             // FT [Bpad][Dpad]: the next network input
-    float* traj;           // [B][D] slot of this step or null
-    const float* sigmas;
+struct PcPredArgs : UpdateCommon {     // ReverseDiffusion / AncestralSampling / None predictor + imputation (sampling.py:210-270, 416-420)
+    // res: not read by the 'none' predictor
     const float* obs;      // completion: observation [B][D] or null
     const float* mask;
+    float* traj;           // [B][D] slot of this step or null
     const float* z_pred;   // injected predictor noise or null (-> Philox STREAM_EM_NOISE); not read under pf / by 'none'
     const float* z_impB;   // injected imputation noise after the predictor, or null
     const float* z_impA;   // injected imputation noise ahead of the NEXT step (corrector 'none' only), or null
-    float t, t_next;       // t_next < 0: no look-ahead imputation
-    int64_t B, Bpad;
-    int D, Dpad, Cp, num_scales, f32, scale_by_sigma;
-    SdeCfg sde;
+    float t_next;          // < 0: no look-ahead imputation
     PcTab tab;             // this step's table entries, by value
-    uint64_t seed;
-    uint32_t step;
     int pred;              // DPOSER_PC_PRED_REVERSE_DIFFUSION / _ANCESTRAL / _NONE
     int pf;
 };
 hipError_t launch_pc_pred_update(const PcPredArgs& a, hipStream_t st);
-struct AldArgs {           // AnnealedLangevinDynamics.update_fn (sampling.py:319-339), one inner step at a shared t
-    const float* res;      // [Bpad][Cp] model output at x
-    const float* noise;    // injected noise [B][D] or null (-> Philox STREAM_LANGEVIN at `step`)
-    const float* sigmas;
-    float* x;              // [B][D] in/out
-    float* x_mean;         // [B][D] out, or null: not stored (a predictor update that follows overwrites it)
-    void* xin;             // FT [Bpad][Dpad]: the new state as the next network input
+struct AldArgs : UpdateCommon {        // AnnealedLangevinDynamics.update_fn (sampling.py:319-339), one inner step at a shared t
+    // x_mean: out, or null: not stored (a predictor update that follows overwrites it)
     const float* obs;      // last inner step of a completion: imputation after the corrector (sampling.py:416-420), else null
     const float* mask;
-    const float* z_imp;    // its injected draw or null (-> Philox STREAM_IMPUTE_A at `imp_step`)
-    float t, alpha, snr;
-    int64_t B, Bpad;
-    int D, Dpad, Cp, num_scales, scale_by_sigma, f32;
-    SdeCfg sde;
-    uint64_t seed;
-    uint32_t step, imp_step;
+    const float* noise;    // injected noise [B][D] or null (-> Philox STREAM_LANGEVIN at `step`)
+    const float* z_imp;    // the imputation's injected draw or null (-> Philox STREAM_IMPUTE_A at `imp_step`)
+    float alpha, snr;
+    uint32_t imp_step;
 };
 hipError_t launch_ald_update(const AldArgs& a, hipStream_t st);
 

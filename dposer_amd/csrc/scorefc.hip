@@ -864,46 +864,54 @@ static int build_time_table_at(dposer_scorefc_s* h, const float* flat, const cha
     DP_TRY(stage_step_labels(h, w, s, &t, 1, st));
     return build_time_table(h, flat, packed, w, w.tt_labels, 0.f, 1, freq, st);
 }
-static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
-                           float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, const float* observation,
-                           const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, const float* freq,
-                           const float* sigmas, int64_t B, void* stream, int pf);
-extern "C" int dposer_em_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
-                                 float* x, float* x_mean, const float* timesteps_host, int32_t start_step, const float* observation,
-                                 const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
-                                 const float* freq, const float* sigmas, int64_t B, void* stream) {
-    return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, -1, observation, mask, noise, seed, traj,
-                           traj_stride, freq, sigmas, B, stream, 0);
+// the fields the samplers' update kernels share (kernels_api.h), from the handle, the workspace and the call
+static UpdateCommon update_common(dposer_scorefc_s* h, const Ws& w, const dposer_sde_desc* sde, const float* sigmas, float* x, float* x_mean,
+                                  uint64_t seed, int64_t B) {
+    UpdateCommon c{};
+    c.res = w.res; c.x = x; c.x_mean = x_mean; c.xin = w.xin; c.sigmas = sigmas;
+    c.B = B; c.Bpad = w.Bpad; c.D = h->D; c.Dpad = h->Dpad; c.Cp = h->Cp; c.num_scales = h->d.num_scales;
+    c.f32 = h->f32; c.scale_by_sigma = sbs_mode(h); c.sde = to_sde(sde); c.seed = seed;
+    return c;
 }
-// probability_flow = True (sde_lib.py:98-105): the same loop with the drift's score term halved and no diffusion.  Same noise layout as
-// dposer_em_sampler; the predictor slots are never read, the two imputation slots of a completion call are.
-extern "C" int dposer_pf_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
-                                 float* x, float* x_mean, const float* timesteps_host, int32_t start_step, const float* observation,
-                                 const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
-                                 const float* freq, const float* sigmas, int64_t B, void* stream) {
-    return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, -1, observation, mask, noise, seed, traj,
-                           traj_stride, freq, sigmas, B, stream, 1);
+// sum_b ||grad_b|| and sum_b ||noise_b|| of the call's samples -> norm_sums[0..1]
+static int langevin_norm_sums(const LangevinArgs& a, float* norm_sums, hipStream_t st) {
+    int nb = 0;
+    DP_HIP_LAUNCH(launch_langevin_norms(a, &nb, st));
+    DP_HIP_LAUNCH(launch_sum_partials2(a.part, nb, norm_sums, st));
+    return DPOSER_OK;
 }
-extern "C" int dposer_em_sampler_steps(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
-                                       float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
-                                       const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
-                                       int32_t traj_stride, const float* freq, const float* sigmas, int64_t B, void* stream) {
-    DP_CHECK_ARG(n_steps >= 0, "n_steps must be >= 0");
-    return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed, traj,
-                           traj_stride, freq, sigmas, B, stream, 0);
-}
-static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
-                           float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, const float* observation,
-                           const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, const float* freq,
-                           const float* sigmas, int64_t B, void* stream, int pf) {
-    DpRange _dp_range(pf ? "dposer_pf_sampler" : "dposer_em_sampler");
+
+// get_pc_sampler.pc_sampler (sampling.py:429-466) for every registered predictor / corrector: include/dposer_hip.h has the contract.
+// THE host loop of the one-call samplers: dposer_em_sampler / _pf_sampler / _em_sampler_steps are (Euler-Maruyama, none) of it, and
+// `entry` names the roctx range after the entry point that was called.  Per loop index: [network + corrector update] x n_steps_each,
+// [imputation], network + predictor update -- every update kernel leaves the new state FT-tiled in w.xin for the next evaluation.
+static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                   const dposer_pc_desc* pc, float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
+                   const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
+                   const float* disc_table_host, float* norm_sums, const float* freq, const float* sigmas, int64_t B, void* stream) {
+    DP_CHECK_ARG(pc, "null argument");
+    const int pred = pc->predictor, corr = pc->corrector, pf = pc->probability_flow ? 1 : 0;
+    DP_CHECK_ARG(pred == DPOSER_PC_PRED_NONE || pred == DPOSER_PC_PRED_EULER_MARUYAMA || pred == DPOSER_PC_PRED_REVERSE_DIFFUSION || pred == DPOSER_PC_PRED_ANCESTRAL, "unknown predictor kind");
+    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || corr == DPOSER_PC_CORR_LANGEVIN || corr == DPOSER_PC_CORR_ALD, "unknown corrector kind");
     DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
     DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
     DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
     DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
     DP_CHECK_ARG((observation == nullptr) == (mask == nullptr), "observation and mask go together");
     DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
+    const SdeCfg sc = to_sde(sde);
+    if (pred == DPOSER_PC_PRED_ANCESTRAL) {      // AncestralSamplingPredictor.__init__, sampling.py:227-231
+        if (sc.kind == SDE_SUBVP) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "ancestral sampling supports the VE and VP SDEs only");
+        if (pf) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "probability flow is not supported by ancestral sampling");
+    }
+    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || pc->n_steps_each >= 1, "n_steps_each must be >= 1 with a corrector");
+    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || norm_sums, "norm_sums is required by the Langevin corrector");
+    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || pc->inv_global_batch > 0.0, "inv_global_batch must be > 0 for the Langevin corrector");
+    const bool pred_table = pred == DPOSER_PC_PRED_ANCESTRAL || (pred == DPOSER_PC_PRED_REVERSE_DIFFUSION && sc.kind != SDE_SUBVP);
+    const bool corr_table = corr != DPOSER_PC_CORR_NONE && sc.kind != SDE_VE;
+    DP_CHECK_ARG(!(pred_table || corr_table) || disc_table_host, "disc_table_host is required: the predictor or corrector reads the SDE's discrete table");
+    DpRange _dp_range(entry);                        // (every argument check is above: a refused call opens no range and launches nothing)
+    g_alg_batch = B;
     hipStream_t st = (hipStream_t)stream;
     const char* packed = (const char*)packed_;
     const int N = sde->N;
@@ -915,24 +923,35 @@ static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* pa
     DP_TRY(stage_step_labels(h, w, sde, timesteps_host + start_step, n_run, st));
     DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_run, freq, st));
 
-    const SdeCfg sc = to_sde(sde);
-    const int k_noise = observation ? 3 : 1;
+    const int nc = corr == DPOSER_PC_CORR_NONE ? 0 : pc->n_steps_each;
+    const int k_noise = nc + (observation ? 3 : 1);
     const int64_t BD = B * h->D;
-    EmUpdateArgs ea;
-    std::memset(&ea, 0, sizeof(ea));
-    ea.x = x; ea.x_mean = x_mean; ea.xin = w.xin; ea.sigmas = sigmas; ea.obs = observation; ea.mask = mask;
-    ea.B = B; ea.Bpad = w.Bpad; ea.D = h->D; ea.Dpad = h->Dpad; ea.Cp = h->Cp; ea.num_scales = h->d.num_scales;
-    ea.f32 = h->f32; ea.scale_by_sigma = sbs_mode(h); ea.sde = sc; ea.seed = seed; ea.pf = pf;
-    // step "-1": imputation ahead of the first predictor call (sampling.py:459) + pack x
-    ea.res = nullptr; ea.t = timesteps_host[start_step]; ea.t_next = timesteps_host[start_step];
-    ea.step = (uint32_t)(start_step - 1);
-    ea.z_impA = (noise && observation) ? noise : nullptr;
-    // Fast path (plain generation: no observation, in-kernel noise, no trajectory): the state stays in HBM as fp32 FT and
+    const UpdateCommon uc = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
+    EmUpdateArgs ea{};                            // Euler-Maruyama predictor, and the stand-alone "imputation + pack" launch
+    static_cast<UpdateCommon&>(ea) = uc; ea.obs = observation; ea.mask = mask; ea.pf = pf;
+    PcPredArgs pa{};
+    static_cast<UpdateCommon&>(pa) = uc; pa.obs = observation; pa.mask = mask; pa.pf = pf; pa.pred = pred;
+    LangevinArgs la{};
+    static_cast<UpdateCommon&>(la) = uc; la.part = w.loss_part; la.norm_sums = norm_sums;
+    la.snr = pc->snr; la.inv_global_batch = (float)pc->inv_global_batch;
+    AldArgs aa{};
+    static_cast<UpdateCommon&>(aa) = uc; aa.snr = pc->snr;
+    aa.x_mean = nullptr;                          // (the predictor update that always follows writes it)
+
+    // The one special case (plain generation: no observation, in-kernel noise, no trajectory): the state stays in HBM as fp32 FT and
     // post_dense + the Euler-Maruyama update are ONE GEMM launch per step (EpiEmStep) -- no `res` round trip, no update kernel.
     // Under probability flow the (ignored) injected predictor noise does not stand in its way.
-    const bool fused = !observation && (pf || !noise) && !traj && h->Cp == h->Dpad;
-    if (fused) ea.x_ft = w.xft;
-    DP_HIP_LAUNCH(launch_em_update(ea, st));
+    const bool fused = pred == DPOSER_PC_PRED_EULER_MARUYAMA && corr == DPOSER_PC_CORR_NONE && !observation && (pf || !noise) && !traj && h->Cp == h->Dpad;
+    if (corr == DPOSER_PC_CORR_NONE) {
+        // step "-1": imputation ahead of the first predictor call (sampling.py:459) + pack x
+        ea.res = nullptr; ea.t = timesteps_host[start_step]; ea.t_next = timesteps_host[start_step];
+        ea.step = (uint32_t)(start_step - 1);
+        ea.z_impA = (noise && observation) ? noise : nullptr;
+        if (fused) ea.x_ft = w.xft;
+        DP_HIP_LAUNCH(launch_em_update(ea, st));
+    } else {
+        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+    }
     if (fused) {
         const int shape = final_shape(w.Bpad);
         for (int i = 0; i < n_run; ++i) {
@@ -956,142 +975,6 @@ static int em_sampler_impl(dposer_scorefc_t h, const float* flat, const void* pa
     }
     for (int i = 0; i < n_run; ++i) {
         const int gi = start_step + i;
-        DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
-        ea.res = w.res;
-        ea.t = timesteps_host[gi];
-        ea.t_next = (i + 1 < n_run) ? timesteps_host[gi + 1] : -1.0f;
-        ea.step = (uint32_t)gi;
-        const float* nz = noise ? noise + (int64_t)i * k_noise * BD : nullptr;
-        ea.z_pred = nz ? nz + (observation ? BD : 0) : nullptr;
-        ea.z_impB = (nz && observation) ? nz + 2 * BD : nullptr;
-        ea.z_impA = (nz && observation && i + 1 < n_run) ? nz + (int64_t)k_noise * BD : nullptr;
-        ea.traj = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
-        DP_HIP_LAUNCH(launch_em_update(ea, st));
-    }
-    return DPOSER_OK;
-}
-
-// LangevinCorrector.update_fn (sampling.py:282-302), one corrector step at a shared t, in two phases around the batch means:
-//   phase 0: pack x, evaluate the network, write sum_b ||grad_b|| and sum_b ||noise_b|| of THIS rank's samples to norm_sums[0..1]
-//   (the caller all-reduces the two floats over the data-parallel ranks -- or not, on one GPU)
-//   phase 1: x_mean = x + step * grad, x = x_mean + sqrt(2 step) * noise with step from norm_sums * inv_global_batch.
-// The workspace keeps the network output between the two phases: nothing else may run on it in between.
-extern "C" int dposer_langevin_step(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
-                                    float* x, float* x_mean, float t, float alpha, float snr, const float* noise, uint64_t seed,
-                                    uint32_t step, float* norm_sums, int32_t phase, double inv_global_batch, const float* freq,
-                                    const float* sigmas, int64_t B, void* stream) {
-    DP_RANGE();
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
-    DP_CHECK_ARG(sde && x && norm_sums && freq && sigmas, "null argument");
-    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
-    DP_CHECK_ARG(phase == 0 || phase == 1, "phase must be 0 (norms) or 1 (update)");
-    DP_CHECK_ARG(phase == 0 || x_mean, "x_mean is required in the update phase");
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, 1, (char*)ws_, w);
-    LangevinArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.res = w.res; a.noise = noise; a.sigmas = sigmas; a.x = x; a.x_mean = x_mean; a.part = w.loss_part; a.norm_sums = norm_sums;
-    a.t = t; a.alpha = alpha; a.snr = snr; a.inv_global_batch = (float)inv_global_batch; a.B = B; a.Bpad = w.Bpad; a.D = h->D; a.Dpad = h->Dpad;
-    a.Cp = h->Cp; a.num_scales = h->d.num_scales; a.scale_by_sigma = sbs_mode(h); a.f32 = h->f32; a.sde = to_sde(sde); a.seed = seed;
-    a.step = step;
-    if (phase == 0) {
-        DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
-        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
-        DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
-        int nb = 0;
-        DP_HIP_LAUNCH(launch_langevin_norms(a, &nb, st));
-        DP_HIP_LAUNCH(launch_sum_partials2(w.loss_part, nb, norm_sums, st));
-    } else {
-        DP_HIP_LAUNCH(launch_langevin_update(a, st));
-    }
-    return DPOSER_OK;
-}
-
-// get_pc_sampler.pc_sampler (sampling.py:429-466) for every registered predictor / corrector: include/dposer_hip.h has the contract.
-// Per loop index: [network + corrector update] x n_steps_each, [imputation], network + predictor update -- every update kernel leaves
-// the new state FT-tiled in w.xin for the next evaluation.  Euler-Maruyama goes through k_em_update and Langevin through its three
-// kernels unchanged; (Euler-Maruyama, none) IS em_sampler_impl.
-extern "C" int dposer_pc_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
-                                 const dposer_pc_desc* pc, float* x, float* x_mean, const float* timesteps_host, int32_t start_step,
-                                 int32_t n_steps, const float* observation, const float* mask, const float* noise, uint64_t seed,
-                                 float* traj, int32_t traj_stride, const float* disc_table_host, float* norm_sums, const float* freq,
-                                 const float* sigmas, int64_t B, void* stream) {
-    DP_CHECK_ARG(pc, "null argument");
-    const int pred = pc->predictor, corr = pc->corrector, pf = pc->probability_flow ? 1 : 0;
-    DP_CHECK_ARG(pred == DPOSER_PC_PRED_NONE || pred == DPOSER_PC_PRED_EULER_MARUYAMA || pred == DPOSER_PC_PRED_REVERSE_DIFFUSION || pred == DPOSER_PC_PRED_ANCESTRAL, "unknown predictor kind");
-    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || corr == DPOSER_PC_CORR_LANGEVIN || corr == DPOSER_PC_CORR_ALD, "unknown corrector kind");
-    if (pred == DPOSER_PC_PRED_EULER_MARUYAMA && corr == DPOSER_PC_CORR_NONE)
-        return em_sampler_impl(h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed, traj,
-                               traj_stride, freq, sigmas, B, stream, pf);
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
-    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
-    DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
-    DP_CHECK_ARG((observation == nullptr) == (mask == nullptr), "observation and mask go together");
-    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
-    const SdeCfg sc = to_sde(sde);
-    if (pred == DPOSER_PC_PRED_ANCESTRAL) {      // AncestralSamplingPredictor.__init__, sampling.py:227-231
-        if (sc.kind == SDE_SUBVP) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "ancestral sampling supports the VE and VP SDEs only");
-        if (pf) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "probability flow is not supported by ancestral sampling");
-    }
-    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || pc->n_steps_each >= 1, "n_steps_each must be >= 1 with a corrector");
-    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || norm_sums, "norm_sums is required by the Langevin corrector");
-    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || pc->inv_global_batch > 0.0, "inv_global_batch must be > 0 for the Langevin corrector");
-    const bool pred_table = pred == DPOSER_PC_PRED_ANCESTRAL || (pred == DPOSER_PC_PRED_REVERSE_DIFFUSION && sc.kind != SDE_SUBVP);
-    const bool corr_table = corr != DPOSER_PC_CORR_NONE && sc.kind != SDE_VE;
-    DP_CHECK_ARG(!(pred_table || corr_table) || disc_table_host, "disc_table_host is required: the predictor or corrector reads the SDE's discrete table");
-    DpRange _dp_range("dposer_pc_sampler");          // (every argument check is above: a refused call opens no range and launches nothing)
-    g_alg_batch = B;
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    const int N = sde->N;
-    const int n_run = (n_steps < 0 || n_steps > N - start_step) ? N - start_step : n_steps;
-    if (n_run == 0) return DPOSER_OK;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, n_run, (char*)ws_, w);
-    DP_TRY(stage_step_labels(h, w, sde, timesteps_host + start_step, n_run, st));
-    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_run, freq, st));
-
-    const int nc = corr == DPOSER_PC_CORR_NONE ? 0 : pc->n_steps_each;
-    const int k_noise = nc + (observation ? 3 : 1);
-    const int64_t BD = B * h->D;
-    EmUpdateArgs ea;                              // Euler-Maruyama predictor, and the stand-alone "imputation + pack" launch
-    std::memset(&ea, 0, sizeof(ea));
-    ea.x = x; ea.x_mean = x_mean; ea.xin = w.xin; ea.sigmas = sigmas; ea.obs = observation; ea.mask = mask;
-    ea.B = B; ea.Bpad = w.Bpad; ea.D = h->D; ea.Dpad = h->Dpad; ea.Cp = h->Cp; ea.num_scales = h->d.num_scales;
-    ea.f32 = h->f32; ea.scale_by_sigma = sbs_mode(h); ea.sde = sc; ea.seed = seed; ea.pf = pf;
-    PcPredArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.x = x; pa.x_mean = x_mean; pa.xin = w.xin; pa.sigmas = sigmas; pa.obs = observation; pa.mask = mask;
-    pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad; pa.Cp = h->Cp; pa.num_scales = h->d.num_scales;
-    pa.f32 = h->f32; pa.scale_by_sigma = sbs_mode(h); pa.sde = sc; pa.seed = seed; pa.pf = pf;
-    pa.pred = pred;
-    LangevinArgs la;
-    std::memset(&la, 0, sizeof(la));
-    la.res = w.res; la.sigmas = sigmas; la.x = x; la.x_mean = x_mean; la.xin = w.xin; la.part = w.loss_part; la.norm_sums = norm_sums;
-    la.snr = pc->snr; la.inv_global_batch = (float)pc->inv_global_batch; la.B = B; la.Bpad = w.Bpad; la.D = h->D; la.Dpad = h->Dpad;
-    la.Cp = h->Cp; la.num_scales = h->d.num_scales; la.scale_by_sigma = sbs_mode(h); la.f32 = h->f32; la.sde = sc; la.seed = seed;
-    AldArgs aa;
-    std::memset(&aa, 0, sizeof(aa));
-    aa.res = w.res; aa.sigmas = sigmas; aa.x = x; aa.x_mean = nullptr; aa.xin = w.xin;      // (x_mean: the predictor update that always follows writes it)
-    aa.snr = pc->snr; aa.B = B; aa.Bpad = w.Bpad;
-    aa.D = h->D; aa.Dpad = h->Dpad; aa.Cp = h->Cp; aa.num_scales = h->d.num_scales; aa.scale_by_sigma = sbs_mode(h); aa.f32 = h->f32;
-    aa.sde = sc; aa.seed = seed;
-
-    if (corr == DPOSER_PC_CORR_NONE) {
-        // step "-1": imputation ahead of the first predictor call (sampling.py:459) + pack x, as dposer_em_sampler does it
-        ea.res = nullptr; ea.t = timesteps_host[start_step]; ea.t_next = timesteps_host[start_step];
-        ea.step = (uint32_t)(start_step - 1);
-        ea.z_impA = (noise && observation) ? noise : nullptr;
-        DP_HIP_LAUNCH(launch_em_update(ea, st));
-    } else {
-        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
-    }
-    for (int i = 0; i < n_run; ++i) {
-        const int gi = start_step + i;
         const float t = timesteps_host[gi];
         const float* nz = noise ? noise + (int64_t)i * k_noise * BD : nullptr;
         const PcTab tab = make_pc_tab(sc, disc_table_host, t);
@@ -1102,9 +985,7 @@ extern "C" int dposer_pc_sampler(dposer_scorefc_t h, const float* flat, const vo
             const uint32_t cstep = (uint32_t)((int64_t)gi * nc + k);
             if (corr == DPOSER_PC_CORR_LANGEVIN) {
                 la.t = t; la.alpha = alpha; la.noise = zc; la.step = cstep;
-                int nb = 0;
-                DP_HIP_LAUNCH(launch_langevin_norms(la, &nb, st));
-                DP_HIP_LAUNCH(launch_sum_partials2(w.loss_part, nb, norm_sums, st));
+                DP_TRY(langevin_norm_sums(la, norm_sums, st));
                 DP_HIP_LAUNCH(launch_langevin_update(la, st));
             } else {
                 const bool last = k + 1 == nc;
@@ -1132,10 +1013,86 @@ extern "C" int dposer_pc_sampler(dposer_scorefc_t h, const float* flat, const vo
             DP_HIP_LAUNCH(launch_em_update(ea, st));
         } else {
             if (pred != DPOSER_PC_PRED_NONE) DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
-            pa.res = w.res; pa.t = t; pa.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; pa.step = (uint32_t)gi; pa.tab = tab;
+            pa.t = t; pa.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; pa.step = (uint32_t)gi; pa.tab = tab;
             pa.z_pred = z_pred; pa.z_impB = z_impB; pa.z_impA = z_impA; pa.traj = slot;
             DP_HIP_LAUNCH(launch_pc_pred_update(pa, st));
         }
+    }
+    return DPOSER_OK;
+}
+extern "C" int dposer_pc_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                 const dposer_pc_desc* pc, float* x, float* x_mean, const float* timesteps_host, int32_t start_step,
+                                 int32_t n_steps, const float* observation, const float* mask, const float* noise, uint64_t seed,
+                                 float* traj, int32_t traj_stride, const float* disc_table_host, float* norm_sums, const float* freq,
+                                 const float* sigmas, int64_t B, void* stream) {
+    return pc_loop(__func__, h, flat, packed_, ws_, sde, pc, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed,
+                   traj, traj_stride, disc_table_host, norm_sums, freq, sigmas, B, stream);
+}
+// The (Euler-Maruyama, none) entries.  probability_flow = True (sde_lib.py:98-105): the same loop with the drift's score term halved and
+// no diffusion; same noise layout, the predictor slots are never read, the two imputation slots of a completion call are.
+static int em_loop(const char* entry, int pf, dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                   float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, const float* observation,
+                   const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, const float* freq,
+                   const float* sigmas, int64_t B, void* stream) {
+    const dposer_pc_desc pc = {DPOSER_PC_PRED_EULER_MARUYAMA, DPOSER_PC_CORR_NONE, 0, pf, 0.f, 0.0};
+    return pc_loop(entry, h, flat, packed_, ws_, sde, &pc, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed, traj,
+                   traj_stride, nullptr, nullptr, freq, sigmas, B, stream);
+}
+extern "C" int dposer_em_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                 float* x, float* x_mean, const float* timesteps_host, int32_t start_step, const float* observation,
+                                 const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
+                                 const float* freq, const float* sigmas, int64_t B, void* stream) {
+    return em_loop(__func__, 0, h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, -1, observation, mask, noise, seed, traj,
+                   traj_stride, freq, sigmas, B, stream);
+}
+extern "C" int dposer_pf_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                 float* x, float* x_mean, const float* timesteps_host, int32_t start_step, const float* observation,
+                                 const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
+                                 const float* freq, const float* sigmas, int64_t B, void* stream) {
+    return em_loop(__func__, 1, h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, -1, observation, mask, noise, seed, traj,
+                   traj_stride, freq, sigmas, B, stream);
+}
+extern "C" int dposer_em_sampler_steps(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                       float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
+                                       const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
+                                       int32_t traj_stride, const float* freq, const float* sigmas, int64_t B, void* stream) {
+    DP_CHECK_ARG(n_steps >= 0, "n_steps must be >= 0");
+    return em_loop(__func__, 0, h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, observation, mask, noise, seed, traj,
+                   traj_stride, freq, sigmas, B, stream);
+}
+
+// LangevinCorrector.update_fn (sampling.py:282-302), one corrector step at a shared t, in two phases around the batch means:
+//   phase 0: pack x, evaluate the network, write sum_b ||grad_b|| and sum_b ||noise_b|| of THIS rank's samples to norm_sums[0..1]
+//   (the caller all-reduces the two floats over the data-parallel ranks -- or not, on one GPU)
+//   phase 1: x_mean = x + step * grad, x = x_mean + sqrt(2 step) * noise with step from norm_sums * inv_global_batch.
+// The workspace keeps the network output between the two phases: nothing else may run on it in between.
+extern "C" int dposer_langevin_step(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                    float* x, float* x_mean, float t, float alpha, float snr, const float* noise, uint64_t seed,
+                                    uint32_t step, float* norm_sums, int32_t phase, double inv_global_batch, const float* freq,
+                                    const float* sigmas, int64_t B, void* stream) {
+    DP_RANGE();
+    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    g_alg_batch = B;
+    DP_CHECK_ARG(sde && x && norm_sums && freq && sigmas, "null argument");
+    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
+    DP_CHECK_ARG(phase == 0 || phase == 1, "phase must be 0 (norms) or 1 (update)");
+    DP_CHECK_ARG(phase == 0 || x_mean, "x_mean is required in the update phase");
+    hipStream_t st = (hipStream_t)stream;
+    const char* packed = (const char*)packed_;
+    Ws w;
+    layout_ws(h, B, DPOSER_WS_SHARED_T, 1, (char*)ws_, w);
+    LangevinArgs a{};
+    static_cast<UpdateCommon&>(a) = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
+    a.xin = nullptr;                              // (the predictor call that follows packs the state)
+    a.noise = noise; a.part = w.loss_part; a.norm_sums = norm_sums;
+    a.t = t; a.alpha = alpha; a.snr = snr; a.inv_global_batch = (float)inv_global_batch; a.step = step;
+    if (phase == 0) {
+        DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
+        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+        DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
+        DP_TRY(langevin_norm_sums(a, norm_sums, st));
+    } else {
+        DP_HIP_LAUNCH(launch_langevin_update(a, st));
     }
     return DPOSER_OK;
 }

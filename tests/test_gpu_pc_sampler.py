@@ -499,6 +499,26 @@ def test_argument_checks_launch_nothing():
         _C.profile_enable(False)
         assert rc != 0 and text in lib.dposer_last_error(), (kind, pred, corr, kw, lib.dposer_last_error())
         assert torch.equal(x, x0) and bool((xm == 7.0).all()) and not stats, (kind, pred, corr, stats)
+    # the three older entries share the loop and its checks
+    call = _Call(m, "subvp", N, B, rows=N)
+    obs = torch.zeros(B, 63, device=DEV)
+    traj = torch.empty(N, B, 63, device=DEV)
+    em_cases = [(e, dict(obs=obs), b"go together") for e in ("dposer_em_sampler", "dposer_pf_sampler")]
+    em_cases += [("dposer_em_sampler_steps", dict(n_steps=-1), b"n_steps")]
+    for e in ("dposer_em_sampler", "dposer_pf_sampler", "dposer_em_sampler_steps"):
+        em_cases += [(e, dict(stride=0), b"traj_stride"), (e, dict(start=N + 1), b"step range")]
+    for entry, kw, text in em_cases:
+        x, xm = x0.clone(), torch.full((B, 63), 7.0, device=DEV)
+        steps = (kw.get("n_steps", 1),) if entry == "dposer_em_sampler_steps" else ()
+        _C.profile_enable(True)
+        rc = getattr(lib, entry)(call.eng.h, _C.ptr(call.flat), _C.ptr(call.packed), _C.ptr(call.ws), C.byref(call.desc), _C.ptr(x), _C.ptr(xm),
+                                 C.c_void_p(ts.ctypes.data), kw.get("start", 0), *steps, _C.ptr(kw.get("obs")), None, None, 0, _C.ptr(traj),
+                                 kw.get("stride", 1), _C.ptr(call.freq), _C.ptr(m.sigmas), B, _C.stream_ptr())
+        torch.cuda.synchronize()
+        stats = _C.profile_collect()
+        _C.profile_enable(False)
+        assert rc != 0 and text in lib.dposer_last_error(), (entry, sorted(kw), lib.dposer_last_error())
+        assert torch.equal(x, x0) and bool((xm == 7.0).all()) and not stats, (entry, sorted(kw), stats)
 
 
 @pytest.mark.parametrize("pred,corr", [("reverse_diffusion", "ald"), ("ancestral_sampling", "none"), ("none", "langevin")])
@@ -517,3 +537,25 @@ def test_a_sub_range_gives_the_bits_of_the_whole_run(pred, corr):
     assert t2.shape == (7, B, 63) and torch.equal(t2, traj[10:17]) and torch.equal(x2, traj[16])
     t3, x3, xm3 = sampling.fused_pc_sample(m, sde, traj[16], ts, start_step=17, traj_stride=1, **kw)
     assert torch.equal(t3, traj[17:]) and torch.equal(x3, x) and torch.equal(xm3, xm)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_an_euler_maruyama_sub_range_gives_the_bits_of_the_whole_run(prec):
+    """dposer_em_sampler_steps over [4, 7) from traj[3] of a whole completion run.  B = 300: ragged rows in the second 256-row tile;
+    D = 63: the last quad partly valid."""
+    from dposer_amd import _C
+    from dposer_amd.algorithms.advanced import sampling
+    cfg, m, p = make_model(39, precision=prec)
+    N, B = 12, 300
+    sde = _sde("subvp", N)
+    z0 = torch.randn(B, 63, device=DEV, generator=torch.Generator(device=DEV).manual_seed(12))
+    ts = torch.linspace(sde.T, 1e-3, N)
+    rs = np.random.RandomState(5)
+    obs, mask = _dev(rs.standard_normal((B, 63))), _dev(rs.choice([0.0, 1.0, 0.25], size=(B, 63)))
+    traj, _, _ = sampling.fused_em_sample(m, sde, z0, ts, seed=5, traj_stride=1, observation=obs, mask=mask)
+    call = _Call(m, "subvp", N, B, rows=3)
+    x, xm, t2 = traj[3].clone(), torch.empty(B, 63, device=DEV), torch.empty(3, B, 63, device=DEV)
+    _C.check(call.eng.lib.dposer_em_sampler_steps(call.eng.h, _C.ptr(call.flat), _C.ptr(call.packed), _C.ptr(call.ws), C.byref(call.desc), _C.ptr(x),
+                                                  _C.ptr(xm), C.c_void_p(ts.numpy().ctypes.data), 4, 3, _C.ptr(obs), _C.ptr(mask), None, 5, _C.ptr(t2),
+                                                  1, _C.ptr(call.freq), _C.ptr(m.sigmas), B, _C.stream_ptr()), "dposer_em_sampler_steps")
+    assert torch.equal(t2, traj[4:7])
