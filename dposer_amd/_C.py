@@ -16,7 +16,7 @@ PRECISIONS = {"bf16": PREC_BF16, "fp32": PREC_FP32, "bf16x3": PREC_BF16X3}
 EMB_POSITIONAL, EMB_FOURIER = 0, 1
 ACTIVATIONS = {"swish": 0, "elu": 1, "relu": 2, "lrelu": 3}      # config.model.nonlinearity -> DPOSER_ACT_*
 SDE_SUBVP, SDE_VP, SDE_VE, SDE_VE_DISCRETE, SDE_VP_DISCRETE = 0, 1, 2, 3, 4
-WS_INFER, WS_SHARED_T, WS_TRAIN = 0, 1, 2
+WS_INFER, WS_SHARED_T, WS_TRAIN, WS_GUIDED = 0, 1, 2, 3
 PC_PRED_NONE, PC_PRED_EULER_MARUYAMA, PC_PRED_REVERSE_DIFFUSION, PC_PRED_ANCESTRAL = 0, 1, 2, 3
 PC_CORR_NONE, PC_CORR_LANGEVIN, PC_CORR_ALD = 0, 1, 2
 
@@ -202,6 +202,8 @@ SIGNATURES = {
                                           vp, vp, i64, vp]),
     "dposer_pc_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), C.POINTER(PcDesc), vp, vp, vp, i32, i32, vp, vp, vp, u64, vp, i32,
                                     vp, vp, vp, vp, i64, vp]),
+    "dposer_guided_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, i32, i32, vp, vp, vp, u64, vp, i32, i32, f32, vp,
+                                        vp, vp, i64, vp]),
     "dposer_langevin_step": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, f32, f32, f32, vp, u64, u32, vp, i32, f64, vp, vp,
                                        i64, vp]),
     "dposer_prior_loss": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, f32, i32, f32, vp, vp, vp, u64,

@@ -19,6 +19,10 @@ the completion imputation and re-tiles x (``fused_pc_supported`` / ``fused_pc_sa
 ``discrete_sigmas`` on the host; the entries of a step travel to the kernels by value.  What stays outside: Langevin under data
 parallelism (``fused_pc_langevin_sample``: three calls per step around the all-reduce of the two norm sums), and probability flow with
 a corrector, other models or SDEs: the generic loop below on top of the HIP score function.
+
+The MCG and DPS completion samplers (``get_guided_sampler``: the loop over ``update_fn_guide``, sampling.py:191-207) run as
+``dposer_guided_sampler``: per step one network evaluation that keeps its activations, the batch-wide residual norm as a fixed-order sum of
+block partials, one dgrad-only backward and one update kernel; other models / SDEs step ``update_fn_guide`` in Python.
 """
 import abc
 import ctypes as C
@@ -270,12 +274,12 @@ def fused_em_supported(sde, model, predictor, corrector, probability_flow, conti
             and isinstance(model, ScoreModelFC))
 
 
-def _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise):
+def _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise, with_backward=False):
     """What the three ``fused_*`` runners set up alike: the engine and its buffers, the state clones, the host timesteps, the trajectory,
     the SDE descriptor and the optional tensors as contiguous fp32.  The workspace is the caller's (its table rows differ)."""
     _C.require_gpu(x, "sampler state")
     p = types.SimpleNamespace(eng=model._engine(), flat=model.flat_params(), B=x.shape[0])
-    p.packed = p.eng.packed(p.flat, with_backward=False, force=not model.freeze_packed)
+    p.packed = p.eng.packed(p.flat, with_backward=with_backward, force=not model.freeze_packed)
     p.x = x.contiguous().float().clone()
     p.x_mean = p.x.clone()
     p.ts_host = timesteps.detach().to("cpu", torch.float32).contiguous()
@@ -507,6 +511,116 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
             return trajs, (x_mean if denoise else x)
 
     return pc_sampler
+
+
+GUIDED_METHODS = ("dps", "mcg")
+
+
+def guided_noise_slots(method):
+    """Slots per loop index of a guided sampler's ``noise`` [n_run, slots, B, D]: the predictor's z, then (MCG) the imputation draw."""
+    return 2 if method == "mcg" else 1
+
+
+def fused_guided_supported(sde, model, continuous):
+    """What ``dposer_guided_sampler`` takes: a ScoreModelFC under the continuous sub-VP / VP score function."""
+    from .model import ScoreModelFC
+    return continuous and isinstance(sde, (sde_lib.subVPSDE, sde_lib.VPSDE)) and isinstance(model, ScoreModelFC) \
+        and sde_lib.sde_desc(sde, continuous) is not None
+
+
+def fused_guided_sample(model, sde, x, timesteps, observation, mask, *, method, grad_step=1.0, start_step=0, run_steps=-1, noise=None, seed=0,
+                        traj_stride=0, continuous=True):
+    """dposer_guided_sampler: loop indices [start_step, start_step + run_steps) (run_steps < 0: to N) of the MCG / DPS loop in ONE library
+    call, then one 4-byte read of the non-finite flag.  x [B, D] initial state (consumed); returns (trajs or None, x, x_mean)."""
+    N = int(sde.N)
+    n_run = N - start_step if (run_steps < 0 or run_steps > N - start_step) else int(run_steps)
+    _C.require_gpu(observation, "guided sampler observation")
+    _C.require_gpu(mask, "guided sampler mask")
+    p = _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, observation, mask, noise, with_backward=True)   # (the dgrad reads the transposed copies)
+    if p.B == 0:
+        return p.traj, p.x, p.x_mean
+    eng, B, packed = p.eng, p.B, p.packed
+    ws = eng.workspace(B, _C.WS_GUIDED, max(n_run, 1), x.device)
+    flag = torch.full((1,), 2 ** 31 - 1, dtype=torch.int32, device=x.device)
+    _C.check(eng.lib.dposer_guided_sampler(eng.h, _C.ptr(p.flat), _C.ptr(packed), _C.ptr(ws), C.byref(p.desc), _C.ptr(p.x), _C.ptr(p.x_mean),
+                                           C.c_void_p(p.ts_host.data_ptr()), int(start_step), int(run_steps), _C.ptr(p.obs), _C.ptr(p.msk),
+                                           _C.ptr(p.nz), int(seed), _C.ptr(p.traj), int(traj_stride or 1), 1 if method == "mcg" else 0,
+                                           float(grad_step), _C.ptr(flag), _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B,
+                                           _C.stream_ptr()), "dposer_guided_sampler")
+    bad = int(flag.item())                           # the call's one host read, after the loop
+    if bad != 2 ** 31 - 1:
+        raise ValueError("Consider reduce the value of parameter: grad_step={} (the gradient is not finite at loop index {})".format(grad_step, bad))
+    return p.traj, p.x, p.x_mean
+
+
+def get_guided_sampler(sde, shape, inverse_scaler, method, grad_step=1.0, continuous=True, denoise=True, eps=1e-3, device="cuda"):
+    """The MCG and DPS completion samplers: the loop of sampling.py:455-461 over ``EulerMaruyamaPredictor.update_fn_guide`` (:191-207),
+    for ``method == "mcg"`` followed by the imputation of :416-420 at every index; no imputation ahead of the step, no corrector.
+
+    ``guided_sampler(model, observation, mask, z=None, start_step=0, *, traj_stride=1, noise=None, seed=None)`` returns
+    ``(trajs [n, B, D], x_mean if denoise else x)`` like ``pc_sampler``; ``noise`` [n_run, 2 if mcg else 1, B, D] injects the draws
+    (predictor z, imputation).  A ScoreModelFC under continuous sub-VP / VP on the GPU runs as ONE ``dposer_guided_sampler`` call;
+    everything else steps ``update_fn_guide`` in Python."""
+    method = str(method).lower()
+    if method not in GUIDED_METHODS:
+        raise ValueError(f"unknown guided sampler method {method!r}: expected one of {GUIDED_METHODS}")
+    call_count = [0]
+
+    def guided_sampler(model, observation, mask, z=None, start_step=0, *, traj_stride=1, noise=None, seed=None):
+        if observation is None or mask is None:
+            raise ValueError("the guided samplers need an observation and a mask")
+        if tuple(observation.shape) != tuple(shape) or tuple(mask.shape) != tuple(shape):
+            raise ValueError(f"observation {tuple(observation.shape)} / mask {tuple(mask.shape)} do not have the sampler's shape {tuple(shape)}")
+        if z is not None and tuple(z.shape) != tuple(shape):
+            raise ValueError(f"z {tuple(z.shape)} does not have the sampler's shape {tuple(shape)}")
+        if not 0 <= start_step <= sde.N:
+            raise ValueError(f"start_step {start_step} outside [0, {sde.N}]")
+        n_run = sde.N - start_step
+        slots = guided_noise_slots(method)
+        if noise is not None and tuple(noise.shape) != (n_run, slots) + tuple(shape):
+            raise ValueError(f"noise {tuple(noise.shape)}: expected {(n_run, slots) + tuple(shape)}")
+        x = sde.prior_sampling(shape).to(device) if z is None else z
+        if fused_guided_supported(sde, model, continuous):
+            call_count[0] += 1
+            if seed is None:
+                seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
+            was_training = model.training
+            model.eval()
+            try:
+                with torch.no_grad():
+                    trajs, x, x_mean = fused_guided_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), observation, mask, method=method,
+                                                           grad_step=grad_step, start_step=start_step, noise=noise, seed=seed,
+                                                           traj_stride=traj_stride, continuous=continuous)
+            finally:
+                model.train(was_training)
+            if trajs is None:
+                trajs = x.new_empty((0,) + tuple(x.shape))
+            return trajs, (x_mean if denoise else x)
+        # the reference semantics, step by step: update_fn_guide (its own autograd round trip and NaN check) + the imputation expression
+        score_fn = mutils.get_score_fn(sde, model, train=False, continuous=continuous)
+        pred = EulerMaruyamaPredictor(sde, score_fn, probability_flow=False)
+        timesteps = torch.linspace(sde.T, eps, sde.N, device=x.device)
+        trajs, x_mean = [], x
+        real_randn_like = torch.randn_like
+        for i in range(start_step, sde.N):
+            vec_t = torch.ones(shape[0], device=x.device) * timesteps[i]
+            nz = None if noise is None else noise[i - start_step]
+            if nz is not None:                       # update_fn_guide draws its z itself: hand it this index's slot
+                torch.randn_like = lambda t, _z=nz[0], **kw: _z
+            try:
+                x, x_mean = pred.update_fn_guide(x.detach(), vec_t, observation, mask, grad_step=grad_step)
+            finally:
+                torch.randn_like = real_randn_like
+            x, x_mean = x.detach(), x_mean.detach()
+            if method == "mcg":                      # sampling.py:416-420
+                mean, std = sde.marginal_prob(observation, vec_t)
+                x = x * (1 - mask) + (mean + (torch.randn_like(x) if nz is None else nz[1]) * std[:, None]) * mask
+            if traj_stride and (i - start_step + 1) % traj_stride == 0:
+                trajs.append(x)
+        trajs = torch.stack(trajs, dim=0) if trajs else x.new_empty((0,) + tuple(x.shape))
+        return trajs, (x_mean if denoise else x)
+
+    return guided_sampler
 
 
 def get_ode_sampler(sde, shape, inverse_scaler, denoise=False, rtol=1e-5, atol=1e-5, method="RK45", eps=1e-3, device="cuda", driver=None,

@@ -799,6 +799,113 @@ template <typename T> __global__ void __launch_bounds__(256) k_ald_update(WithSd
 }
 hipError_t launch_ald_update(const AldArgs& a, hipStream_t st) { return launch_quads(k_ald_update<float>, k_ald_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
 // row-major [B][D] fp32 -> FT [Bpad][Dpad] network input (zero padded)
+// ---- MCG / DPS guided Euler-Maruyama step (sampling.py:191-207 around RSDE.sde(guide=True), sde_lib.py:98-109) -------------------------
+//   y0 = (x + sigma^2 score) / alpha;  r = obs mask - y0 mask;  norm = ||r||_F over the WHOLE batch (:201)
+//   grad = d norm / d x = u / alpha + J_score^T [(sigma^2 / alpha) u],  u = -mask r / norm
+//   x = y_mean + g sqrt(-dt) z - grad_step grad;  x_mean = y_mean;  MCG: the imputation of :416-420 behind it
+// Two passes around the grid-wide norm and the network's dgrad: `resid` writes the upstream gradient of the backward WITHOUT the 1 / norm
+// (the backward is linear in it) and the partial sums of r^2; `update` recomputes score and r from the same inputs, divides by the norm and
+// steps.  k_langevin_norms / k_langevin_update's shape.
+struct GuidedScal { float mc, sd, sd2, beta, g, sds, usig; };
+template <typename A> __device__ __forceinline__ GuidedScal guided_scalars(const A& a, const SdeDev& sde) {
+    const SdeAt at = sde_at(sde, a.t);
+    GuidedScal k;
+    k.mc = at.mc; k.sd = at.sd; k.sd2 = at.sd * at.sd; k.beta = at.beta; k.g = at.g; k.sds = at.sd_score;   // return_alpha_sigma: alpha = mc, sigma = std
+    k.usig = launch_usig(a, at.label);
+    return k;
+}
+// r = obs mask - y0 mask and the score, for one element
+__device__ __forceinline__ float guided_resid(const SdeDev& sde, const GuidedScal& k, float res, float x, float obs, float m, float* score_out) {
+    const float score = sde_score(sde, res / k.usig, k.sds);                       // model.py:194, utils.py:162
+    const float y0 = (x + k.sd2 * score) / k.mc;                                    // sampling.py:200
+    *score_out = score;
+    return obs * m - y0 * m;                                                        // :201
+}
+template <typename T> __global__ void __launch_bounds__(256) k_guided_resid(WithSde<GuidedArgs> d) {
+    const GuidedArgs& a = d.a;
+    const int qc = a.Cp >> 2;
+    const int64_t total = a.Bpad * qc;
+    const GuidedScal k = guided_scalars(a, d.sde);
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qc;
+        const int c = (int)(i % qc) * 4;
+        f32x4 dr = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const int64_t o = s * a.D + c + r;
+                const float m = a.mask[o];
+                float score;
+                const float rr = guided_resid(d.sde, k, a.res[s * a.Cp + c + r], a.x[o], a.obs[o], m, &score);
+                acc += rr * rr;
+                // autograd of the norm's argument down to res, without the 1 / norm: d / d y0 = -mask r, / alpha, * sigma^2 (the score's share),
+                // d score / d model (sde_score), / used_sigmas
+                const float gscore = ((-(m * rr)) / k.mc) * k.sd2;
+                const float gmodel = d.sde.kind == SDE_VE ? gscore : -(gscore / k.sds);
+                dr[r] = gmodel / k.usig;
+            }
+        }
+        store_quad_ft<T>(a.dres, s, c, a.Cp, dr);
+    }
+    const float tot = block_sum_256(acc);
+    if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
+}
+hipError_t launch_guided_resid(const GuidedArgs& a, int* nblocks, hipStream_t st) {
+    const WithSde<GuidedArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
+    const int g = grid_for(a.Bpad * (a.Cp >> 2), 256, 1024);
+    *nblocks = g;
+    hipLaunchKernelGGL(a.f32 ? k_guided_resid<float> : k_guided_resid<__bf16>, dim3(g), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+template <typename T> __global__ void __launch_bounds__(256) k_guided_update(WithSde<GuidedArgs> d) {
+    const GuidedArgs& a = d.a;
+    const int qx = a.Dpad >> 2;
+    const int QD = (a.D + 3) >> 2;
+    const int64_t total = a.Bpad * qx;
+    const GuidedScal k = guided_scalars(a, d.sde);
+    const float norm = sqrtf(a.norm_sq[0]);                                         // torch.norm: the square root of the sum of squares
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qx;              // quad index fastest: row-major [B][D] streams are read/written contiguously
+        const int q = (int)(i % qx);
+        const int c = q * 4;
+        f32x4 xn = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+            float zp[4], zi[4];
+            if (!a.z_pred) normals4((uint64_t)s * QD + q, STREAM_EM_NOISE, a.step, a.seed, zp);
+            if (a.project && !a.z_imp) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_B, a.step, a.seed, zi);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const int64_t o = s * a.D + c + r;
+                const float x0 = a.x[o], m = a.mask[o], obs = a.obs[o];
+                float score;
+                const float rr = guided_resid(d.sde, k, a.res[s * a.Cp + c + r], x0, obs, m, &score);
+                // rsde.sde: drift = -0.5 beta x - g^2 score                           sde_lib.py:98-104
+                float drift = (-0.5f * k.beta) * x0;
+                drift = drift - (k.g * k.g) * score;
+                const float y_mean = x0 + drift * d.sde.dt;                            // sampling.py:196
+                const float y_hat = y_mean + (k.g * d.sde.sqrt_mdt) * (a.z_pred ? a.z_pred[o] : zp[r]);   // :197
+                // d norm / d x: the direct share of y0 and the network's, both still times norm; norm == 0: torch's norm backward gives 0
+                const float gn = (-(m * rr)) / k.mc + a.dx[o];
+                const float grad = norm == 0.0f ? 0.0f : gn / norm;
+                if (!isfinite(grad)) bad = true;                                       // :203-204
+                float x = y_hat - a.grad_step * grad;                                  // :205
+                a.x_mean[o] = y_mean;
+                if (a.project) x = impute(x, m, obs, k.mc, a.z_imp ? a.z_imp[o] : zi[r], k.sd);   // :416-420
+                if (a.traj) a.traj[o] = x;
+                a.x[o] = x;
+                xn[r] = x;
+            }
+        }
+        store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
+    }
+    if (bad) atomicMin(a.nonfinite, (int32_t)a.step);
+}
+hipError_t launch_guided_update(const GuidedArgs& a, hipStream_t st) { return launch_quads(k_guided_update<float>, k_guided_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
+
 template <typename T> __global__ void __launch_bounds__(256) k_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, int D, int Dpad) {
     const int qx = Dpad >> 2;
     const int64_t total = Bpad * qx;

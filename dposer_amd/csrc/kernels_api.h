@@ -243,6 +243,25 @@ struct AldArgs : UpdateCommon {        // AnnealedLangevinDynamics.update_fn (sa
 };
 hipError_t launch_ald_update(const AldArgs& a, hipStream_t st);
 
+// ---- one-call MCG / DPS guided sampler (sampling.py:191-207 around sde_lib.py:98-109): two passes around the batch-wide norm and the dgrad ----
+struct GuidedArgs : UpdateCommon {
+    // res: post_dense output at x, kept with the activations; x_mean: out = y_mean (the mean does not carry the guidance)
+    const float* obs;      // observation [B][D]
+    const float* mask;     // mask [B][D]
+    float* traj;           // [B][D] slot of this step or null
+    const float* z_pred;   // injected predictor noise [B][D] or null (-> Philox STREAM_EM_NOISE at `step`)
+    const float* z_imp;    // MCG: injected imputation noise or null (-> Philox STREAM_IMPUTE_B at `step`)
+    void* dres;            // resid pass: FT [Bpad][Cp], d norm / d res TIMES norm (the backward is linear: the update pass divides)
+    float* part;           // resid pass: per-block partial sums of r^2
+    const float* norm_sq;  // update pass: [1] = sum of the partials
+    const float* dx;       // update pass: [B][D] = J_res^T dres
+    int32_t* nonfinite;    // update pass: atomicMin of `step` where an element of the gradient is not finite
+    float grad_step;
+    int project;           // 1: MCG's imputation behind the step
+};
+hipError_t launch_guided_resid(const GuidedArgs& a, int* nblocks, hipStream_t st);
+hipError_t launch_guided_update(const GuidedArgs& a, hipStream_t st);
+
 struct DsmArgs {           // get_sde_loss_fn tail (losses.py:121-131) + d loss / d res
     const float* res;      // [Bpad][Cp]
     const float* t;        // [Bpad]

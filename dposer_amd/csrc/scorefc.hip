@@ -554,6 +554,13 @@ static void layout_ws(const dposer_scorefc_s* h, int64_t B, int mode, int n_step
         }
         w.slabs = (float*)take(slab_elems * 4);
         w.slab_elems = slab_elems;
+        if (mode == DPOSER_WS_GUIDED) {      // behind the unchanged training layout: the time-bias table of the guided sampler's steps
+            w.npad = round_up(n_steps < 1 ? 1 : n_steps, 32);
+            w.tt_labels = (float*)take(w.npad * 4);
+            w.tt_emb = (float*)take(w.npad * E * 4);
+            w.tt_temb = (float*)take(w.npad * E * 4);
+            w.table = (float*)take(w.npad * (int64_t)L * H * 4);
+        }
     }
     w.total = p;
 }
@@ -1963,6 +1970,87 @@ extern "C" int dposer_scorefc_backward(dposer_scorefc_t h, const float* flat, co
     da.f32 = h->f32;
     DP_HIP_LAUNCH(launch_dres_from_dout(da, st));
     return backward_core(h, flat, packed, w, B, train_mode != 0, seed, step, flat_grad, dx, nullptr, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// MCG / DPS guided samplers (sampling.py:191-207 over sde_lib.py:98-109; include/dposer_hip.h has the contract)
+// ------------------------------------------------------------------------------------------------
+// forward_core_train at a shared t: the time branch is row `row` of the time-bias table (run_shared_t_layers' form of the layer), every
+// layer input / normalised activation is kept for backward_core, no dropout.
+static int forward_core_guided(dposer_scorefc_s* h, const float* flat, const char* packed, Ws& w, int64_t row, int64_t B, hipStream_t st) {
+    const int L = h->L;
+    DP_TRY(split_act(h, w.xin, w.p_xin, w.Bpad, h->Dpad, st));
+    const float* trow = w.table + row * (int64_t)L * h->H;
+    for (int l = 0; l < L; ++l) {
+        const void* in = l == 0 ? (const void*)w.xin : (const void*)w.hbuf[l - 1];
+        const Planes& in_pl = l == 0 ? w.p_xin : w.p_h[l - 1];
+        const void* resid = (l >= 2 && (l % 2) == 0) ? w.hbuf[l - 2] : nullptr;
+        const LayerOff& lo = h->layer[l];
+        const int shape = gn_shape(w.Bpad, h->H, h->gs, !h->f32);
+        const int kx = lo.kin_pad / h->KBS, ke = h->E / h->KBS;
+        g_next_flops = 2.0 * (double)B * h->H * lo.kin;
+        GemmArgs g = gemm_args(packed + h->pk_wl[l], (kx + ke) * h->wk, h->H / (shape_ct(shape) * 32), (int)(w.Bpad / (shape_st(shape) * 32)));
+        add_act(h, g, in, in_pl, kx);
+        GNParams p;
+        p.bias = trow + (int64_t)l * h->H;
+        p.gamma = flat + lo.gamma; p.beta = flat + lo.beta; p.out = w.hbuf[l]; p.resid = resid; p.xhat = w.xhat[l]; p.aux = w.aux[l];
+        p.H = h->H; p.drop = drop_cfg(h, false, l, 0, 0); p.act = h->d.activation;
+        p.outT = nullptr; p.Spad = w.Bpad;                     // (no weight gradient: no transposed copy)
+        p.out_hi = h->x3 ? w.p_h[l].hi : nullptr;
+        p.out_lo = h->x3 ? w.p_h[l].lo : nullptr;
+        if (h->x3 && !((l % 2) == 0 && l + 2 < L)) p.out = nullptr;
+        DP_HIP_LAUNCH(gemm_gn(gemm_prec(h), true, shape, g, p, st, h->gs));
+    }
+    return run_post(h, flat, packed, w.hbuf[L - 1], w.p_h[L - 1], w.res, B, w.Bpad, st);
+}
+
+// Per loop index: network with kept activations -> k_guided_resid (upstream gradient times norm, partial sums of r^2) -> k_sum_partials ->
+// dgrad-only backward (backward_core without a flat gradient) -> k_guided_update, which leaves the new state FT-tiled in w.xin.
+extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                     float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
+                                     const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
+                                     int32_t traj_stride, int32_t project, float grad_step, int32_t* nonfinite_step, const float* freq,
+                                     const float* sigmas, int64_t B, void* stream) {
+    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
+    DP_CHECK_ARG(observation && mask, "observation and mask are required");
+    DP_CHECK_ARG(nonfinite_step, "nonfinite_step is required");
+    DP_CHECK_ARG(sde->kind == DPOSER_SDE_SUBVP || sde->kind == DPOSER_SDE_VP, "the guided sampler takes the continuous sub-VP and VP score functions");
+    DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
+    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
+    DP_CHECK_ARG(project == 0 || project == 1, "project must be 0 (DPS) or 1 (MCG)");
+    DP_RANGE();                                      // (every argument check is above: a refused call opens no range and launches nothing)
+    g_alg_batch = B;
+    hipStream_t st = (hipStream_t)stream;
+    const char* packed = (const char*)packed_;
+    const int N = sde->N;
+    const int n_run = (n_steps < 0 || n_steps > N - start_step) ? N - start_step : n_steps;
+    if (n_run == 0) return DPOSER_OK;
+    Ws w;
+    layout_ws(h, B, DPOSER_WS_GUIDED, n_run, (char*)ws_, w);
+    DP_TRY(stage_step_labels(h, w, sde, timesteps_host + start_step, n_run, st));
+    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_run, freq, st));
+    const int k_noise = project ? 2 : 1;
+    const int64_t BD = B * h->D;
+    GuidedArgs ga{};
+    static_cast<UpdateCommon&>(ga) = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
+    ga.obs = observation; ga.mask = mask; ga.dres = w.dres; ga.part = w.loss_part; ga.norm_sq = w.scalar; ga.dx = w.zbuf;
+    ga.nonfinite = nonfinite_step; ga.grad_step = grad_step; ga.project = project;
+    DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+    for (int i = 0; i < n_run; ++i) {
+        const int gi = start_step + i;
+        const float* nz = noise ? noise + (int64_t)i * k_noise * BD : nullptr;
+        ga.t = timesteps_host[gi]; ga.step = (uint32_t)gi;
+        ga.z_pred = nz; ga.z_imp = (nz && project) ? nz + BD : nullptr;
+        ga.traj = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
+        DP_TRY(forward_core_guided(h, flat, packed, w, i, B, st));
+        int nb = 0;
+        DP_HIP_LAUNCH(launch_guided_resid(ga, &nb, st));
+        DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, w.scalar, st));
+        DP_TRY(backward_core(h, flat, packed, w, B, false, 0, 0, nullptr, w.zbuf, nullptr, st));
+        DP_HIP_LAUNCH(launch_guided_update(ga, st));
+    }
+    return DPOSER_OK;
 }
 
 extern "C" int dposer_grad_sqnorm(const float* grad, int64_t n, float* scratch, void* stream) {

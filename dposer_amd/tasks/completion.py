@@ -109,8 +109,36 @@ class DPoserComp:
         return observation * mask + x.detach() * (1.0 - mask)
 
 
+SOLVERS = ("dposer", "scoresde", "mcg", "dps")
+
+
+class _TaskArgs:
+    """What the samplers read of run/demo.py's ``args``: the task name (sampling.py:416, 451)."""
+
+    def __init__(self, task):
+        self.task = task
+
+
+def _completion_solver(solver, model, sde, continuous, shape, device, solver_kwargs):
+    """``complete(observation, mask) -> completion`` for the diffusion solvers DPoser's completion table is compared against: ScoreSDE
+    imputation (run/demo.py:389-394: get_sampling_fn's sampler with args.task == 'completion'), MCG and DPS (the loop over
+    update_fn_guide, sampling.py:191-207: ``sampling.get_guided_sampler``).  The sampler's return value is the completion, unblended."""
+    from ..algorithms.advanced import sampling
+    kw = dict(solver_kwargs or {})
+    eps = kw.pop("eps", 1e-3)
+    extra = {k: kw.pop(k) for k in ("traj_stride", "seed") if k in kw}
+    extra.setdefault("traj_stride", 0)               # the evaluation keeps no trajectory
+    if solver == "scoresde":
+        fn = sampling.get_pc_sampler(sde, shape, sampling.EulerMaruyamaPredictor, sampling.NoneCorrector, lambda v: v, snr=kw.pop("snr", 0.16),
+                                     continuous=continuous, denoise=kw.pop("denoise", True), eps=eps, device=device, **kw)
+        args = _TaskArgs("completion")
+        return lambda observation, mask: fn(model, observation=observation, mask=mask, args=args, **extra)[1]
+    fn = sampling.get_guided_sampler(sde, shape, lambda v: v, solver, continuous=continuous, eps=eps, device=device, **kw)
+    return lambda observation, mask: fn(model, observation, mask, **extra)[1]
+
+
 def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs", hypo=1, batch_size=16384, continuous=True,
-                        num_replicas=None, rank=None, optimize_kwargs=None):
+                        num_replicas=None, rank=None, optimize_kwargs=None, solver="dposer", solver_kwargs=None):
     """The evaluation loop of run/completion.py:215-323 (``inference``) for the poses of one test set, without its process / CLI
     shell: this rank's contiguous shard (DistributedEvalSampler arithmetic, EvaSampler.py:78-106) in batches of ``batch_size``
     with ``drop_last`` like the reference's DataLoader -> create_mask -> ``hypo`` completions -> de-normalise -> Evaler
@@ -118,7 +146,11 @@ def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs
 
     Nothing synchronises with the host inside the loop: the per-sample metrics stay device tensors, and the end is ONE all-reduce
     of (sum, count) pairs (``distributed.reduce_metric_means``) instead of ``gather_object`` of every value (:300-305).
-    ``poses`` [N, D] normalised test poses (the dataset's ``poses`` tensor); returns ``({metric: mean}, samples evaluated here)``."""
+    ``poses`` [N, D] normalised test poses (the dataset's ``poses`` tensor); returns ``({metric: mean}, samples evaluated here)``.
+    ``solver``: "dposer" (the optimisation above, ``optimize_kwargs``) or one of the diffusion samplers "scoresde" | "mcg" | "dps"
+    (``solver_kwargs``: ``grad_step`` for MCG / DPS, ``eps``, ``denoise``, ``seed``); each hypothesis is one sampler call."""
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown completion solver {solver!r}: expected one of {SOLVERS}")
     from .. import distributed as ddp
     from ..dataset.AMASS import Evaler
     from ..utils.misc import create_mask
@@ -128,11 +160,15 @@ def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs
     dev = next(model.parameters()).device
     evaler = Evaler(body_model=body_model, part=part)
     comp = DPoserComp(model, sde, continuous, batch_size=batch_size)      # one object: its call counter keys the in-kernel noise
+    complete = None if solver == "dposer" else _completion_solver(solver, model, sde, continuous, (batch_size, poses.shape[1]), dev, solver_kwargs)
     results, done = [], 0
     for b0 in range(lo, hi - batch_size + 1, batch_size) if hi - lo >= batch_size else []:
         batch = poses[b0:b0 + batch_size].to(dev, non_blocking=True)
         mask, observation = create_mask(batch, part=part)
-        outs = torch.stack([comp.optimize(observation, mask, **(optimize_kwargs or {})) for _ in range(hypo)], dim=1)
+        if complete is None:
+            outs = torch.stack([comp.optimize(observation, mask, **(optimize_kwargs or {})) for _ in range(hypo)], dim=1)
+        else:
+            outs = torch.stack([complete(observation, mask) for _ in range(hypo)], dim=1)
         preds = normalizer.offline_denormalize(outs, to_axis=True)
         gts = normalizer.offline_denormalize(batch, to_axis=True)
         results.append(evaler.multi_eval_bodys(preds, gts, as_tensors=True))

@@ -109,7 +109,8 @@ void dposer_scorefc_tuning_reload(void);
  * masks the reference drew with torch's generator through the fused training step. */
 int dposer_scorefc_debug_set_dropout_masks(dposer_scorefc_t h, const unsigned char* keep, int64_t batch);
 
-enum { DPOSER_WS_INFER = 0, DPOSER_WS_SHARED_T = 1, DPOSER_WS_TRAIN = 2 };
+/* DPOSER_WS_GUIDED: the DPOSER_WS_TRAIN layout (every activation kept) followed by a time-bias table of n_steps rows (dposer_guided_sampler) */
+enum { DPOSER_WS_INFER = 0, DPOSER_WS_SHARED_T = 1, DPOSER_WS_TRAIN = 2, DPOSER_WS_GUIDED = 3 };
 int64_t dposer_scorefc_workspace_bytes(dposer_scorefc_t h, int64_t batch, int32_t mode, int32_t n_steps);
 
 /* ScoreModelFC.forward(batch, t) in eval mode -- model.py:141-196.
@@ -396,6 +397,34 @@ int dposer_pc_sampler(dposer_scorefc_t h, const float* flat_params, const void* 
                       int32_t n_steps, const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
                       int32_t traj_stride, const float* disc_table_host, float* norm_sums, const float* freq, const float* sigmas,
                       int64_t batch, void* stream);
+
+/* The MCG / DPS guided samplers for pose completion, one call: the loop of sampling.py:455-461 over
+ * EulerMaruyamaPredictor.update_fn_guide (sampling.py:191-207, "this can be used to implement MCG and DPS") around
+ * RSDE.sde(guide=True) (sde_lib.py:98-109).  Loop indices [start_step, start_step + n_steps) (n_steps < 0: to N) are enqueued, nothing
+ * synchronises with the host, all memory is the caller's.  Arguments as dposer_em_sampler_steps (observation and mask are required), plus
+ *   project          0 = DPS (the guided step alone), 1 = MCG (the guided step, then the imputation of sampling.py:416-420 at t);
+ *   grad_step        the step along -d norm / d x;
+ *   nonfinite_step   DEVICE int32 the caller sets to INT32_MAX: on return (after the stream has drained) the smallest loop index at
+ *                    which an element of the gradient was not finite (sampling.py:203-204 raises there; this loop keeps running).
+ * Per loop index i (t = timesteps_host[i], dt = -1 / N):
+ *   score = score_fn(x, t): one network evaluation that keeps its activations (eval mode, no dropout);
+ *   y_mean = x + (-1/2 beta x - g^2 score) dt,  y_hat = y_mean + g sqrt(-dt) z;
+ *   y0 = (x + sigma^2 score) / alpha,  r = observation * mask - y0 * mask,  norm = ||r||_F over all batch * D entries of THIS call
+ *   (torch.norm of the whole tensor, :201: the samples couple; no collective);
+ *   grad = d norm / d x = u / alpha + J_score^T [(sigma^2 / alpha) u],  u = -mask r / norm: one dgrad-only backward through the kept
+ *   activations (no weight-gradient GEMM); norm == 0 gives grad = 0, as torch's norm backward does;
+ *   x = y_hat - grad_step * grad,  x_mean = y_mean;  MCG: x = x (1 - mask) + (mean_t(observation) + std_t z_imp) mask;
+ *   trajectory entry when (i - start_step + 1) % traj_stride == 0.
+ * The norm is a sum of per-block partials in a fixed order (no floating-point atomics): the same inputs give the same bits.
+ * noise [n_run][project ? 2 : 1][B][D]: the predictor's z, then the imputation draw; NULL -> Philox STREAM_EM_NOISE at i and
+ * STREAM_IMPUTE_B at i (the draws of dposer_em_sampler's predictor and of the imputation behind it).
+ * DPOSER_SDE_SUBVP / DPOSER_SDE_VP (continuous score function).  `packed` must hold the backward copies (with_backward = 1).
+ * Workspace: DPOSER_WS_GUIDED with n_run table rows. */
+int dposer_guided_sampler(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws, const dposer_sde_desc* sde,
+                          float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
+                          const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
+                          int32_t traj_stride, int32_t project, float grad_step, int32_t* nonfinite_step, const float* freq,
+                          const float* sigmas, int64_t batch, void* stream);
 
 /* DPoserComp.optimize -- run/completion.py:167-207 (loss :131-149, weights :151-155): `n_steps` Adam steps on the pose batch
  * x [B, D] (in: the initial value, i.e. the observation; out: the optimised variable -- the caller applies the final
