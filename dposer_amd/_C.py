@@ -119,6 +119,17 @@ class RigidAlignArgs(C.Structure):
                 ("aligned", C.c_void_p), ("mean_dist", C.c_void_p)]
 
 
+class PosePairErrorsArgs(C.Structure):
+    """dposer_pose_pair_errors_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("body", C.c_void_p), ("ws_ref", C.c_void_p), ("ws_hyp", C.c_void_p), ("joints_ref", C.c_void_p), ("joints_hyp", C.c_void_p),
+                ("v_shaped", C.c_void_p), ("v_shaped_batched", C.c_int32), ("skin_k", C.c_int32), ("skin_idx", C.c_void_p), ("skin_w", C.c_void_p),
+                ("transl_ref", C.c_void_p), ("transl_hyp", C.c_void_p), ("vert_list", C.c_void_p), ("joint_rows", C.c_void_p),
+                ("num_listed_vertices", C.c_int32), ("num_listed_rows", C.c_int32), ("max_listed_row", C.c_int32), ("hypotheses", C.c_int32),
+                ("extra_vertex_ids", C.c_void_p), ("lmk_tri", C.c_void_p), ("lmk_bary", C.c_void_p), ("batch", C.c_int64), ("scale", C.c_float),
+                ("min_into", C.c_int32), ("mpvpe", C.c_void_p), ("mpjpe", C.c_void_p), ("mpvpe_h", C.c_void_p), ("mpjpe_h", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
 class RegressJointsArgs(C.Structure):
     """dposer_regress_joints_args (include/dposer_hip.h), field for field."""
     _fields_ = [("vertices", C.c_void_p), ("batch", C.c_int64), ("num_vertices", C.c_int32), ("row_ptr", C.c_void_p), ("col", C.c_void_p),
@@ -277,6 +288,8 @@ SIGNATURES = {
                                                    vp, i64, f32, vp, vp, vp, i64, vp]),
     "dposer_lbs_temporal_in_backward_ok": (i32, [vp, i32, i64]),
     "dposer_lbs_forward_front": (C.c_int, [vp, vp, vp, C.POINTER(vp), C.POINTER(i32), i32, vp, i32, vp, vp, i64, vp]),
+    "dposer_pose_pair_errors_scratch_bytes": (i64, [vp, i64, i32, i32]),
+    "dposer_pose_pair_errors": (C.c_int, [C.POINTER(PosePairErrorsArgs), vp]),
     "dposer_lbs_backward_temporal": (C.c_int, [vp, vp, vp, vp, C.POINTER(vp), C.POINTER(i32), i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp,
                                                i64, f32, vp, vp, i64, C.POINTER(vp), i64, vp]),
     "dposer_lbs_posedirs_bwd_packed_bytes": (i64, [vp]),

@@ -66,6 +66,24 @@ class _ShapeBlendFunction(torch.autograd.Function):
         return None, out
 
 
+def _marshal_segments(core, segs, B):
+    """The pose segments of one call as the C ABI takes them: (device pointers [_MAX_SEG], joint counts [_MAX_SEG], the detached
+    contiguous fp32 tensors behind the pointers -- None where a segment is absent).  ``segs`` is in ``core.segments`` order."""
+    segp = (C.c_void_p * _MAX_SEG)()
+    segj = (C.c_int32 * _MAX_SEG)()
+    keep = []
+    for i, ((_, nj), t) in enumerate(zip(core.segments, segs)):
+        segj[i] = nj
+        if t is not None:
+            t = t.detach().reshape(B, nj * 3).contiguous().float()
+            keep.append(t)
+            segp[i] = t.data_ptr()
+        else:
+            keep.append(None)
+            segp[i] = None
+    return segp, segj, keep
+
+
 class _LBSFunction(torch.autograd.Function):
     """dposer_lbs_forward / dposer_lbs_backward as one differentiable op.
     inputs: core, n_seg_tensors..., v_shaped, j_rest, transl (any may be None)."""
@@ -76,19 +94,8 @@ class _LBSFunction(torch.autograd.Function):
         dev = core.v_template.device
         h, lib = core._handle(), _C.lib()
         ws = torch.empty(lib.dposer_lbs_workspace_bytes(h, B), dtype=torch.uint8, device=dev)     # private: read back in backward
-        segp = (C.c_void_p * _MAX_SEG)()
-        segj = (C.c_int32 * _MAX_SEG)()
         nseg = len(core.segments)
-        keep = []
-        for i, ((_, nj), t) in enumerate(zip(core.segments, segs)):
-            segj[i] = nj
-            if t is not None:
-                t = t.detach().reshape(B, nj * 3).contiguous().float()
-                keep.append(t)
-                segp[i] = t.data_ptr()
-            else:
-                keep.append(None)
-                segp[i] = None
+        segp, segj, keep = _marshal_segments(core, segs, B)
         vs, jr = v_shaped.detach().contiguous(), j_rest.detach().contiguous()
         tr = None if transl is None else transl.detach().contiguous().float()
         verts = torch.empty(B, core.V, 3, dtype=torch.float32, device=dev)
@@ -413,6 +420,34 @@ class _SMPLCore(nn.Module):
                                         _C.stream_ptr()), "dposer_lbs_forward")
         return self._output(verts, joints, segs, betas, expression, B, dev, return_full_pose)
 
+    def lbs_front(self, *, rest=None, betas=None, expression=None, transl=None, **segs):
+        """The front half of the LBS forward (``dposer_lbs_forward_front``: FK, skinning transforms, pose-blend offsets) for one batch,
+        outside autograd: ``Struct(ws, joints, v_shaped, j_rest, batched, transl, batch)``.  ``ws`` is a fresh workspace holding the
+        transforms and the offsets, ``joints [B, J + n_extra + n_lmk, 3]`` has only ``[:, :J]`` written -- what the kernels that skin
+        in registers read (``dposer_pose_pair_errors``).  ``segs``: the pose keywords of ``forward``; ``rest``: a
+        ``(v_shaped, j_rest, batched)`` triple to use instead of ``rest_shape(betas, expression)``."""
+        unknown = set(segs) - {name for name, _ in self.segments}
+        if unknown:
+            raise ValueError(f"model_type {self.model_type!r} has no pose segments {sorted(unknown)}")
+        given = [t for t in segs.values() if t is not None]
+        if not given:
+            raise ValueError("lbs_front needs at least one pose segment")
+        B, dev = int(given[0].shape[0]), given[0].device
+        _C.require_gpu(given[0], "BodyModel input")
+        if self.v_template.device != dev:
+            raise _C.DPoserHipError("BodyModel buffers and inputs are on different devices; call .to(device)")
+        with torch.no_grad():
+            v_shaped, j_rest, batched = rest if rest is not None else self.rest_shape(betas, expression)
+        segp, segj, keep = _marshal_segments(self, [segs.get(name) for name, _ in self.segments], B)
+        vs, jr = v_shaped.detach().contiguous(), j_rest.detach().contiguous()
+        tr = None if transl is None else transl.detach().contiguous().float()
+        h, lib = self._handle(), _C.lib()
+        ws = torch.empty(lib.dposer_lbs_workspace_bytes(h, B), dtype=torch.uint8, device=dev)
+        joints = torch.empty(B, self.J + self.n_extra + self.n_lmk, 3, dtype=torch.float32, device=dev)
+        _C.check(lib.dposer_lbs_forward_front(h, _C.ptr(ws), _C.ptr(self._packed_posedirs()), segp, segj, len(self.segments), _C.ptr(jr),
+                                              1 if batched else 0, _C.ptr(tr), _C.ptr(joints), B, _C.stream_ptr()), "dposer_lbs_forward_front")
+        return Struct(ws=ws, joints=joints, v_shaped=vs, j_rest=jr, batched=batched, transl=tr, batch=B, segments=keep)
+
     def _zeros(self, B, n, dev):
         """The all-zero default of a pose segment / betas that was not passed (smplx hands out its own default parameters the same
         way: a shared tensor, not a fresh one).  Cached per (B, n): seven fill launches per call were 34 us of a 0.77 ms forward at
@@ -477,6 +512,10 @@ class BodyModel(nn.Module):
             out["pose_jaw"] = o.jaw_pose
             out["pose_eye"] = pose_eye
         return out if return_dict else Struct(**out)
+
+    def lbs_front(self, pose_body, root_orient=None, betas=None, trans=None, rest=None):
+        """Front half of ``forward`` for [B, 63] body poses, no vertices and no autograd: see ``_SMPLCore.lbs_front``."""
+        return self.bm.lbs_front(rest=rest, betas=betas, transl=trans, global_orient=root_orient, body_pose=pose_body)
 
     def fk_joints(self, pose_body, root_orient=None, trans=None, n_joints=22):
         """Joints-only fast path (no vertices): [B, 63] -> [B, n_joints, 3]."""

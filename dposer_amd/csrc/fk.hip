@@ -1231,15 +1231,25 @@ extern "C" int dposer_lbs_pack_posedirs(dposer_body_t h, const float* posedirs, 
     FK_HIP_LAUNCH(launch_pack(js, posedirs, packed, (hipStream_t)stream));
     return DPOSER_OK;
 }
+// The forward workspace of `batch` poses, as byte offsets from its base: the ONE place its layout is written (the front half fills it;
+// the skinning backward and dposer_pose_pair_errors read A and the offsets back out of it).
+struct LbsWsView {
+    int64_t pf, A, offsets, pf_split, bytes;
+};
+static LbsWsView lbs_ws_view(dposer_body_t h, int64_t batch) {
+    const int64_t Bpad = lbs_pad_batch(batch);
+    LbsWsView w;
+    int64_t p = 0;
+    w.pf = p; p += round_up(Bpad * lbs_ppad(h->d.num_joints) * 4, 256);          // pose feature FT32
+    w.A = p; p += round_up(batch * h->d.num_joints * 12 * 4, 256);               // A [batch][J][12]
+    w.offsets = p; p += round_up(batch * lbs_cpad(h->d.num_vertices) * 4, 256);  // offsets [batch][Cpad]
+    w.pf_split = p; p += round_up(Bpad * 3 * lbs_ppad(h->d.num_joints) * 2, 256);   // pose feature as bf16 [hi | hi | lo]
+    w.bytes = p;
+    return w;
+}
 extern "C" int64_t dposer_lbs_workspace_bytes(dposer_body_t h, int64_t batch) {
     if (!h || batch <= 0) return -1;
-    const int64_t Bpad = lbs_pad_batch(batch);
-    int64_t p = 0;
-    p += round_up(Bpad * lbs_ppad(h->d.num_joints) * 4, 256);          // pose feature FT32
-    p += round_up(batch * h->d.num_joints * 12 * 4, 256);              // A
-    p += round_up(batch * lbs_cpad(h->d.num_vertices) * 4, 256);       // offsets
-    p += round_up(Bpad * 3 * lbs_ppad(h->d.num_joints) * 2, 256);      // pose feature as bf16 [hi | hi | lo]
-    return p;
+    return lbs_ws_view(h, batch).bytes;
 }
 
 // FK + pose-blend GEMM of the LBS forward (steps 1 and 2); A / offsets: where the skinning stage finds its inputs in `ws`
@@ -1255,11 +1265,11 @@ static int lbs_forward_front(dposer_body_t h, void* ws, const void* posedirs_pac
     const int64_t Bpad = lbs_pad_batch(batch);
     const int Ppad = lbs_ppad(J);
     const int64_t Cpad = lbs_cpad(V);
-    char* p = (char*)ws;
-    float* pf = (float*)p; p += round_up(Bpad * Ppad * 4, 256);
-    float* A = (float*)p; p += round_up(batch * J * 12 * 4, 256);
-    float* offsets = (float*)p; p += round_up(batch * Cpad * 4, 256);
-    __bf16* pf_split = (__bf16*)p;
+    const LbsWsView w = lbs_ws_view(h, batch);
+    float* pf = (float*)((char*)ws + w.pf);
+    float* A = (float*)((char*)ws + w.A);
+    float* offsets = (float*)((char*)ws + w.offsets);
+    __bf16* pf_split = (__bf16*)((char*)ws + w.pf_split);
     const int n_total = J + h->d.num_extra + h->d.num_landmarks;
 
     // 1. FK: posed joints -> joints[:, :J], skinning transforms A, pose feature (FT32 operand of the blend GEMM)
@@ -1562,6 +1572,354 @@ extern "C" int dposer_lbs_forward_temporal_grad(dposer_body_t h, void* ws, const
     const dim3 grid((unsigned)vchunks, (unsigned)(n_seq * a.nseg));
     if (v_shaped_batched) hipLaunchKernelGGL((k_skin_temporal<NV, true>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((k_skin_temporal<NV, false>), grid, dim3(256), lds, st, a);
+    FK_HIP_LAUNCH(hipGetLastError());
+    return DPOSER_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// Pose-pair errors: MPVPE / MPJPE of H hypothesis bodies against one reference body per sample, minimum over the hypotheses
+// (lib/dataset/AMASS.py:275-316, Evaler.eval_bodys / multi_eval_bodys).  The evaluator needs the vertices for one number per sample, so
+// they never reach HBM: k_skin_temporal's structure walking hypotheses instead of frames.  A workgroup owns NV x 256 entries of one
+// sample's vertex list, keeps their ELL rows, the rest shape and the REFERENCE body's vertices in registers, and walks the hypotheses
+// with the next one's transforms and offsets in flight (transforms double-buffered in LDS, one barrier per hypothesis, as k_skin_run).
+// Vertices = k_skin_x4's two expressions under DP_SKIN_FP; distance and sums with contraction off.
+// Sums: a wave adds its 64 distances by xor butterfly and leaves ONE float per (sample, hypothesis, 256-entry block, wave) in `part`;
+// k_pair_err_final adds a block's four waves ((p0 + p1) + p2) + p3 and the blocks in block order.  No atomics; the order depends on the
+// list length alone -- not on NV, the grid, B, H or where the sample sits in the batch.
+// ------------------------------------------------------------------------------------------------
+struct PairErrArgs {
+    SkinArgs ref, hyp;         // offsets / A / transl of the two workspaces; rest shape and ELL tables in both (verts unused)
+    const int32_t* vert_list;  // [n] or null (entry i = vertex i)
+    int n, nblk;               // list length, ceil(n / 256)
+    int H;                     // hypotheses per sample; hypothesis (b, h) is row b * H + h of `hyp`
+    float* part;               // [B][H][nblk][4]
+};
+// vertex v of pose `row` of one workspace, transforms at A (LDS or global): the two DP_SKIN_FP expressions of k_skin / k_skin_x4
+__device__ __forceinline__ void pair_skin_vertex(const SkinArgs& s, const float* A, int64_t row, const float* vs_row, int v, float (&q)[3]) {
+    DP_SKIN_FP
+    const float* off = s.offsets + row * s.ld_off + (int64_t)v * 3;
+    const float px = vs_row[(int64_t)v * 3] + off[0], py = vs_row[(int64_t)v * 3 + 1] + off[1], pz = vs_row[(int64_t)v * 3 + 2] + off[2];
+    float tr[3] = {0.f, 0.f, 0.f};
+    if (s.transl) { tr[0] = s.transl[row * 3]; tr[1] = s.transl[row * 3 + 1]; tr[2] = s.transl[row * 3 + 2]; }
+    float T[12];
+    if (s.K == 4) {                                                 // k_skin_x4's blend, written out under this function's pragma
+        const f32x4 w4 = *reinterpret_cast<const f32x4*>(s.skin_w + (int64_t)v * 4);
+        const int4 j4 = *reinterpret_cast<const int4*>(s.skin_idx + (int64_t)v * 4);
+        const int jj[4] = {j4.x, j4.y, j4.z, j4.w};
+#pragma unroll
+        for (int i = 0; i < 12; ++i) T[i] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f32x4* Aj = reinterpret_cast<const f32x4*>(A) + jj[k] * 3;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const f32x4 row = Aj[r];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) T[4 * r + i] += w4[k] * row[i];
+            }
+        }
+    } else {
+        skin_transform(s, A, v, T);                                 // k_skin's general loop
+    }
+    q[0] = T[0] * px + T[1] * py + T[2] * pz + T[3] + tr[0];
+    q[1] = T[4] * px + T[5] * py + T[6] * pz + T[7] + tr[1];
+    q[2] = T[8] * px + T[9] * py + T[10] * pz + T[11] + tr[2];
+}
+__device__ __forceinline__ float pair_distance(const float (&q)[3], const float (&r)[3]) {
+    DP_SKIN_FP_OFF
+    const float ax = q[0] - r[0], ay = q[1] - r[1], az = q[2] - r[2];
+    return sqrtf(ax * ax + ay * ay + az * az);
+}
+__device__ __forceinline__ float pair_wave_sum(float x) {
+    DP_SKIN_FP_OFF
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) x += __shfl_xor(x, sh);
+    return x;
+}
+// skin_k == 4 and J <= 64: the pipelined form
+template <int NV> __global__ void __launch_bounds__(256, NV >= 4 ? 3 : 4) k_pair_err(PairErrArgs a) {
+    DP_SKIN_FP
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [2][J][12]
+    const SkinArgs& s = a.ref;
+    const int JA = s.J * 12;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nchunk = (a.nblk + NV - 1) / NV;
+    const int64_t b = blockIdx.x / nchunk;
+    const int blk0 = (int)(blockIdx.x % nchunk) * NV;
+    const float* vs_row = s.v_shaped + (s.v_shaped_batched ? b * s.V * 3 : 0);
+    uint32_t vo[NV];                                               // 3 x the vertex: its first float in a row of offsets (32-bit: V * 3 < 2^31)
+    f32x4 w4[NV];
+    uint32_t jp[NV];                                               // the four joint ids of the ELL row, a byte each (J <= 64)
+    float vs[NV][3];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int i = (blk0 + u) * 256 + threadIdx.x;
+        const int ic = i < a.n ? i : a.n - 1;                       // clamp: the tail threads work on a valid entry and are not counted
+        const int vc = a.vert_list ? a.vert_list[ic] : ic;
+        vo[u] = (uint32_t)vc * 3u;
+        w4[u] = *reinterpret_cast<const f32x4*>(s.skin_w + (int64_t)vc * 4);
+        const int4 j4 = *reinterpret_cast<const int4*>(s.skin_idx + (int64_t)vc * 4);
+        jp[u] = (uint32_t)j4.x | ((uint32_t)j4.y << 8) | ((uint32_t)j4.z << 16) | ((uint32_t)j4.w << 24);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vs[u][c] = vs_row[vo[u] + c];
+    }
+    // pose t = -1 is the reference body, t = 0 .. H - 1 the hypotheses
+    float an[3];                                                   // the next pose's transforms on their way into LDS
+    float on[NV][3], trn[3];                                       // its offsets and translation
+    auto load = [&](int t) __attribute__((always_inline)) {
+        const SkinArgs& p = t < 0 ? a.ref : a.hyp;
+        const int64_t row = t < 0 ? b : b * a.H + t;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int e = threadIdx.x + i * 256;
+            an[i] = e < JA ? p.A[row * JA + e] : 0.f;
+        }
+        const float* off_row = p.offsets + row * p.ld_off;
+#pragma unroll
+        for (int u = 0; u < NV; ++u)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) on[u][c] = off_row[vo[u] + c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) trn[c] = p.transl ? p.transl[row * 3 + c] : 0.f;
+    };
+    auto store_A = [&](float* dst) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int e = threadIdx.x + i * 256;
+            if (e < JA) dst[e] = an[i];
+        }
+    };
+    load(-1);
+    store_A(smem);
+    float rq[NV][3];                                               // the reference body's vertices
+    int cur = 0;
+#pragma unroll 1
+    for (int t = -1; t < a.H; ++t) {
+        __syncthreads();                                           // sA[cur] complete; every wave is done with sA[cur ^ 1]
+        const float* sA = smem + cur * JA;
+        float p[NV][3];
+#pragma unroll
+        for (int u = 0; u < NV; ++u)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[u][c] = vs[u][c] + on[u][c];
+        const float tr[3] = {trn[0], trn[1], trn[2]};
+        if (t + 1 < a.H) load(t + 1);                              // in flight behind this pose's arithmetic
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int jj[4] = {(int)(jp[u] & 255u), (int)((jp[u] >> 8) & 255u), (int)((jp[u] >> 16) & 255u), (int)(jp[u] >> 24)};
+            float T[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) T[i] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const f32x4* Aj = reinterpret_cast<const f32x4*>(sA) + jj[k] * 3;    // 16-byte reads: see k_skin_x4
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const f32x4 row = Aj[r];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) T[4 * r + i] += w4[u][k] * row[i];
+                }
+            }
+            float q[3];
+            q[0] = T[0] * p[u][0] + T[1] * p[u][1] + T[2] * p[u][2] + T[3] + tr[0];
+            q[1] = T[4] * p[u][0] + T[5] * p[u][1] + T[6] * p[u][2] + T[7] + tr[1];
+            q[2] = T[8] * p[u][0] + T[9] * p[u][1] + T[10] * p[u][2] + T[11] + tr[2];
+            if (t < 0) {
+                rq[u][0] = q[0]; rq[u][1] = q[1]; rq[u][2] = q[2];
+            } else {
+                const float d = pair_distance(q, rq[u]);
+                const float dsum = pair_wave_sum((blk0 + u) * 256 + (int)threadIdx.x < a.n ? d : 0.f);
+                if (lane == 0 && blk0 + u < a.nblk) a.part[(((b * a.H + t) * a.nblk) + blk0 + u) * 4 + wave] = dsum;
+            }
+            __builtin_amdgcn_sched_barrier(0);                     // one vertex at a time, as k_skin_temporal
+        }
+        if (t + 1 < a.H) store_A(smem + (cur ^ 1) * JA);
+        cur ^= 1;
+    }
+}
+// any ELL width, any joint count: one 256-entry block per workgroup, the transforms staged per pose
+__global__ void __launch_bounds__(256) k_pair_err_general(PairErrArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [J][12]
+    const SkinArgs& s = a.ref;
+    const int JA = s.J * 12;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t b = blockIdx.x / a.nblk;
+    const int blk = (int)(blockIdx.x % a.nblk);
+    const float* vs_row = s.v_shaped + (s.v_shaped_batched ? b * s.V * 3 : 0);
+    const int i = blk * 256 + threadIdx.x;
+    const bool live = i < a.n;
+    const int ic = live ? i : a.n - 1;
+    const int v = a.vert_list ? a.vert_list[ic] : ic;
+    float rq[3] = {0.f, 0.f, 0.f};
+    for (int t = -1; t < a.H; ++t) {
+        const SkinArgs& p = t < 0 ? a.ref : a.hyp;
+        const int64_t row = t < 0 ? b : b * a.H + t;
+        __syncthreads();                                           // every wave is done with the previous pose's transforms
+        for (int e = threadIdx.x; e < JA; e += 256) smem[e] = p.A[row * JA + e];
+        __syncthreads();
+        float q[3];
+        pair_skin_vertex(p, smem, row, vs_row, v, q);
+        if (t < 0) {
+            rq[0] = q[0]; rq[1] = q[1]; rq[2] = q[2];
+        } else {
+            const float dsum = pair_wave_sum(live ? pair_distance(q, rq) : 0.f);
+            if (lane == 0) a.part[(((b * a.H + t) * a.nblk) + blk) * 4 + wave] = dsum;
+        }
+    }
+}
+
+struct PairFinalArgs {
+    SkinArgs ref, hyp;
+    const float* joints_ref;     // [B][ld_j]
+    const float* joints_hyp;     // [B * H][ld_j]
+    int64_t ld_j;
+    const int32_t* joint_rows;   // [m] or null (entry r = row r)
+    int m, n_extra, n_lmk;
+    const int32_t* extra_ids;
+    const int32_t* lmk_tri;
+    const float* lmk_bary;
+    const float* part;           // [B][H][nblk][4]
+    int n, nblk, H;
+    float scale;
+    int min_into;
+    float *mpvpe, *mpjpe, *mpvpe_h, *mpjpe_h;
+};
+// row r of the LBS joint output of pose `row`: a tree joint as the front half wrote it, or the vertex gather / barycentric sum of
+// k_extra_joints over vertices skinned here (the transforms are read from global memory: at most 3 vertices per row)
+__device__ __forceinline__ void pair_joint_row(const PairFinalArgs& a, const SkinArgs& s, const float* joints, int64_t row, const float* vs_row, int r,
+                                               float (&q)[3]) {
+    const float* A = s.A + row * s.J * 12;
+    if (r < s.J) {
+        const float* p = joints + row * a.ld_j + (int64_t)r * 3;
+        q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
+    } else if (r < s.J + a.n_extra) {
+        if (!a.extra_ids) { q[0] = q[1] = q[2] = __builtin_nanf(""); return; }
+        pair_skin_vertex(s, A, row, vs_row, a.extra_ids[r - s.J], q);
+    } else {
+        DP_SKIN_FP_OFF
+        if (!a.lmk_tri || !a.lmk_bary) { q[0] = q[1] = q[2] = __builtin_nanf(""); return; }
+        const int l = r - s.J - a.n_extra;
+        float x = 0.f, y = 0.f, z = 0.f;
+#pragma unroll
+        for (int f = 0; f < 3; ++f) {                               // k_extra_joints' order
+            float p[3];
+            pair_skin_vertex(s, A, row, vs_row, a.lmk_tri[l * 3 + f], p);
+            const float w = a.lmk_bary[l * 3 + f];
+            x += p[0] * w; y += p[1] * w; z += p[2] * w;
+        }
+        q[0] = x; q[1] = y; q[2] = z;
+    }
+}
+// min with torch.min's NaN rule: a NaN on either side stays
+__device__ __forceinline__ float pair_min(float best, float x) { return (x < best || x != x) ? x : best; }
+// one workgroup per sample: joint term, block-ordered vertex sums, scale, minimum over the hypotheses
+__global__ void __launch_bounds__(128) k_pair_err_final(PairFinalArgs a) {
+    DP_SKIN_FP_OFF
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [m][3] reference rows | [2] wave sums
+    float* sred = smem + (size_t)a.m * 3;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t b = blockIdx.x;
+    const float* vs_row = a.ref.v_shaped + (a.ref.v_shaped_batched ? b * a.ref.V * 3 : 0);
+    for (int r = threadIdx.x; r < a.m; r += 128) {                  // (a thread reads back only the rows it wrote: no barrier)
+        float q[3];
+        pair_joint_row(a, a.ref, a.joints_ref, b, vs_row, a.joint_rows ? a.joint_rows[r] : r, q);
+        smem[r * 3] = q[0]; smem[r * 3 + 1] = q[1]; smem[r * 3 + 2] = q[2];
+    }
+    float best_v = 0.f, best_j = 0.f;
+    if (threadIdx.x == 0 && a.min_into) { best_v = a.mpvpe[b]; best_j = a.mpjpe[b]; }
+    for (int h = 0; h < a.H; ++h) {
+        const int64_t row = b * a.H + h;
+        float acc = 0.f;
+        for (int r = threadIdx.x; r < a.m; r += 128) {
+            float q[3];
+            pair_joint_row(a, a.hyp, a.joints_hyp, row, vs_row, a.joint_rows ? a.joint_rows[r] : r, q);
+            const float rr[3] = {smem[r * 3], smem[r * 3 + 1], smem[r * 3 + 2]};
+            acc += pair_distance(q, rr);
+        }
+        acc = pair_wave_sum(acc);
+        if (lane == 0) sred[wave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float ej = (sred[0] + sred[1]) / (float)a.m * a.scale;
+            float sum = 0.f;
+            const f32x4* p4 = reinterpret_cast<const f32x4*>(a.part) + row * a.nblk;
+            for (int k = 0; k < a.nblk; ++k) {
+                const f32x4 p = p4[k];
+                sum += ((p[0] + p[1]) + p[2]) + p[3];
+            }
+            const float ev = sum / (float)a.n * a.scale;
+            if (a.mpvpe_h) a.mpvpe_h[row] = ev;
+            if (a.mpjpe_h) a.mpjpe_h[row] = ej;
+            best_v = (h == 0 && !a.min_into) ? ev : pair_min(best_v, ev);
+            best_j = (h == 0 && !a.min_into) ? ej : pair_min(best_j, ej);
+        }
+        __syncthreads();                                           // sred is free again
+    }
+    if (threadIdx.x == 0) { a.mpvpe[b] = best_v; a.mpjpe[b] = best_j; }
+}
+
+static constexpr int kPairFinalMaxRows = 4096;                     // joint rows whose reference positions one workgroup keeps in LDS
+extern "C" int64_t dposer_pose_pair_errors_scratch_bytes(dposer_body_t h, int64_t batch, int32_t hypotheses, int32_t listed_vertices) {
+    if (!h || batch <= 0 || hypotheses <= 0) return -1;
+    const int64_t n = listed_vertices > 0 ? listed_vertices : h->d.num_vertices;
+    return round_up(batch * hypotheses * ceil_div(n, 256) * 4 * (int64_t)sizeof(float), 256);
+}
+extern "C" int dposer_pose_pair_errors(const dposer_pose_pair_errors_args* g, void* stream) {
+    DP_RANGE();
+    DP_CHECK_ARG(g, "args is NULL");
+    dposer_body_t h = g->body;
+    DP_CHECK_ARG(h && g->ws_ref && g->ws_hyp && g->joints_ref && g->joints_hyp && g->v_shaped && g->skin_idx && g->skin_w && g->scratch,
+                 "null argument (body, ws_ref, ws_hyp, joints_ref, joints_hyp, v_shaped, skin_idx, skin_w and scratch are required)");
+    DP_CHECK_ARG(g->mpvpe && g->mpjpe, "null output (mpvpe and mpjpe are required)");
+    DP_CHECK_ARG(g->batch >= 1 && g->hypotheses >= 1 && g->skin_k >= 1, "batch, hypotheses and skin_k must be >= 1");
+    const int J = h->d.num_joints, V = h->d.num_vertices, n_extra = h->d.num_extra, n_lmk = h->d.num_landmarks;
+    const int n_total = J + n_extra + n_lmk;
+    DP_CHECK_ARG(!g->vert_list || (g->num_listed_vertices >= 1), "num_listed_vertices must be >= 1 when vert_list is given");
+    DP_CHECK_ARG(!g->joint_rows || (g->num_listed_rows >= 1), "num_listed_rows must be >= 1 when joint_rows is given");
+    const int n = g->vert_list ? g->num_listed_vertices : V;
+    const int m = g->joint_rows ? g->num_listed_rows : n_total;
+    DP_CHECK_ARG(m <= kPairFinalMaxRows, "at most 4096 listed joint rows");
+    DP_CHECK_ARG(((uintptr_t)g->ws_ref & 255) == 0 && ((uintptr_t)g->ws_hyp & 255) == 0 && ((uintptr_t)g->scratch & 255) == 0,
+                 "ws_ref, ws_hyp and scratch must be 256-byte aligned");
+    const int max_row = g->joint_rows ? g->max_listed_row : n_total - 1;
+    DP_CHECK_ARG(max_row >= 0 && max_row < n_total, "max_listed_row outside the rows of the LBS joint output");
+    DP_CHECK_ARG(max_row < J || n_extra == 0 || g->extra_vertex_ids, "a listed joint row >= num_joints needs extra_vertex_ids");
+    DP_CHECK_ARG(max_row < J + n_extra || n_lmk == 0 || (g->lmk_tri && g->lmk_bary), "a listed landmark row needs lmk_tri and lmk_bary");
+    const int64_t B = g->batch;
+    const int H = g->hypotheses;
+    const int nblk = (int)ceil_div(n, 256);
+    DP_CHECK_ARG(B * H < ((int64_t)1 << 31) / nblk, "batch x hypotheses x vertex blocks must stay below 2^31");
+    hipStream_t st = (hipStream_t)stream;
+    const LbsWsView wr = lbs_ws_view(h, B), wh = lbs_ws_view(h, B * H);
+    PairErrArgs a;
+    SkinArgs& r = a.ref;
+    r.offsets = (const float*)((const char*)g->ws_ref + wr.offsets); r.ld_off = lbs_cpad(V); r.v_shaped = g->v_shaped;
+    r.v_shaped_batched = g->v_shaped_batched; r.A = (const float*)((const char*)g->ws_ref + wr.A); r.skin_idx = g->skin_idx; r.skin_w = g->skin_w;
+    r.K = g->skin_k; r.J = J; r.V = V; r.transl = g->transl_ref; r.verts = nullptr;
+    a.hyp = r;
+    a.hyp.offsets = (const float*)((const char*)g->ws_hyp + wh.offsets); a.hyp.A = (const float*)((const char*)g->ws_hyp + wh.A);
+    a.hyp.transl = g->transl_hyp;
+    a.vert_list = g->vert_list; a.n = n; a.nblk = nblk; a.H = H; a.part = (float*)g->scratch;
+    if (g->skin_k == 4 && J * 12 <= 768) {
+        // vertices per workgroup from the list length alone: long lists amortise the transforms over 1024 entries, short ones keep
+        // more workgroups per sample
+        if (n >= 2048) {
+            hipLaunchKernelGGL((k_pair_err<4>), dim3((unsigned)(B * ceil_div(nblk, 4))), dim3(256), 2 * J * 12 * sizeof(float), st, a);
+        } else {
+            hipLaunchKernelGGL((k_pair_err<1>), dim3((unsigned)(B * nblk)), dim3(256), 2 * J * 12 * sizeof(float), st, a);
+        }
+    } else {
+        DP_CHECK_ARG((size_t)J * 12 * sizeof(float) <= 64 * 1024, "too many joints");
+        hipLaunchKernelGGL(k_pair_err_general, dim3((unsigned)(B * nblk)), dim3(256), J * 12 * sizeof(float), st, a);
+    }
+    FK_HIP_LAUNCH(hipGetLastError());
+    PairFinalArgs f;
+    f.ref = a.ref; f.hyp = a.hyp; f.joints_ref = g->joints_ref; f.joints_hyp = g->joints_hyp; f.ld_j = (int64_t)n_total * 3;
+    f.joint_rows = g->joint_rows; f.m = m; f.n_extra = n_extra; f.n_lmk = n_lmk; f.extra_ids = g->extra_vertex_ids; f.lmk_tri = g->lmk_tri;
+    f.lmk_bary = g->lmk_bary; f.part = a.part; f.n = n; f.nblk = nblk; f.H = H; f.scale = g->scale; f.min_into = g->min_into ? 1 : 0;
+    f.mpvpe = g->mpvpe; f.mpjpe = g->mpjpe; f.mpvpe_h = g->mpvpe_h; f.mpjpe_h = g->mpjpe_h;
+    hipLaunchKernelGGL(k_pair_err_final, dim3((unsigned)B), dim3(128), ((size_t)m * 3 + 4) * sizeof(float), st, f);
     FK_HIP_LAUNCH(hipGetLastError());
     return DPOSER_OK;
 }
@@ -2776,9 +3134,10 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
     const int Ppad = lbs_ppad(J);
     const int64_t prow = round_up((J - 1) * 9, 128);
     // forward workspace layout (dposer_lbs_forward)
-    const char* pf_ = (const char*)ws_fwd;
-    const float* A = (const float*)(pf_ + round_up(Bpad * Ppad * 4, 256));
-    const float* offsets = (const float*)((const char*)A + round_up(batch * J * 12 * 4, 256));
+    const LbsWsView wf = lbs_ws_view(h, batch);
+    const char* pf_ = (const char*)ws_fwd + wf.pf;
+    const float* A = (const float*)((const char*)ws_fwd + wf.A);
+    const float* offsets = (const float*)((const char*)ws_fwd + wf.offsets);
     char* p = (char*)ws_bwd;
     float* vp = (float*)p; p += round_up(batch * V * 3 * 4, 256);
     float* dv_fixed = (float*)p;                                        // [B][U][3] corrected vertex-gradient rows of the joint fold (U <= V)

@@ -167,9 +167,34 @@ class Evaler:
             self.vert_idx = torch.tensor(np.array(getattr(BodySegIndices, part)))
         else:
             self.joint_idx = self.vert_idx = None
+        # the fused path's lists (utils.metric.pose_pair_errors): range-checked here, one int32 device copy per device
+        from ..utils.metric import IndexList
+        core = getattr(body_model, "bm", None)
+        self._vert_list = self._row_list = self._list_error = None
+        if part is not None and core is not None:
+            try:
+                self._vert_list = IndexList(self.vert_idx, core.V, "part vertex list")
+                self._row_list = IndexList(self.joint_idx, core.J + core.n_extra + core.n_lmk, "part joint list")
+            except ValueError as e:       # a body model smaller than the part tables: the unfused path fails when it indexes; so does this one
+                self._list_error = e
+            else:
+                if core.v_template.is_cuda:
+                    self._vert_list.on(core.v_template.device)
+                    self._row_list.on(core.v_template.device)
 
-    def eval_bodys(self, outs, gts):
-        """outs, gts [b, 63] axis-angle body poses -> {'mpvpe_all': [b], 'mpjpe_body': [b]} in mm (device tensors)."""
+    def _fused(self, outs, gts):
+        from ..utils.metric import pose_pair_errors
+        if self._list_error is not None:
+            raise self._list_error
+        r = pose_pair_errors(self.body_model, gts, outs, vert_idx=self._vert_list, joint_idx=self._row_list, scale=1000.0)
+        return {"mpvpe_all": r["mpvpe"], "mpjpe_body": r["mpjpe"]}
+
+    def eval_bodys(self, outs, gts, fused=False):
+        """outs, gts [b, 63] axis-angle body poses -> {'mpvpe_all': [b], 'mpjpe_body': [b]} in mm (device tensors).  ``fused``: one
+        ``dposer_pose_pair_errors`` call on the front halves of the two bodies instead of two whole-mesh forwards and torch
+        reductions -- same keys and units, values equal to fp32 rounding of the sums."""
+        if fused:
+            return self._fused(outs, gts)
         with torch.no_grad():
             body_gt = self.body_model(pose_body=gts)
             body_out = self.body_model(pose_body=outs)
@@ -179,10 +204,14 @@ class Evaler:
                 dj = dj[:, self.joint_idx.to(dj.device)]
             return {"mpvpe_all": torch.sqrt((dv ** 2).sum(-1)).mean(-1) * 1000, "mpjpe_body": torch.sqrt((dj ** 2).sum(-1)).mean(-1) * 1000}
 
-    def multi_eval_bodys(self, outs, gts, as_tensors=False):
+    def multi_eval_bodys(self, outs, gts, as_tensors=False, fused=False):
         """outs [b, hypo, 63]: minimum over hypotheses (AMASS.py:300-316).  Returns numpy vectors like the reference, or -- with
         ``as_tensors`` -- device tensors, so a whole evaluation run never synchronises with the host until
-        ``distributed.reduce_metric_means`` at the end."""
+        ``distributed.reduce_metric_means`` at the end.  ``fused``: all hypotheses in one ``pose_pair_errors`` call (the ground-truth body
+        is formed once, no vertex tensor is written)."""
+        if fused:
+            out = self._fused(outs, gts)
+            return out if as_tensors else {k: v.cpu().numpy() for k, v in out.items()}
         res = [self.eval_bodys(outs[:, h].contiguous(), gts) for h in range(outs.shape[1])]
         out = {k: torch.stack([r[k] for r in res], 0).min(0).values for k in ("mpvpe_all", "mpjpe_body")}
         return out if as_tensors else {k: v.cpu().numpy() for k, v in out.items()}

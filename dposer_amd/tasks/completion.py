@@ -138,7 +138,7 @@ def _completion_solver(solver, model, sde, continuous, shape, device, solver_kwa
 
 
 def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs", hypo=1, batch_size=16384, continuous=True,
-                        num_replicas=None, rank=None, optimize_kwargs=None, solver="dposer", solver_kwargs=None):
+                        num_replicas=None, rank=None, optimize_kwargs=None, solver="dposer", solver_kwargs=None, fused_eval=False):
     """The evaluation loop of run/completion.py:215-323 (``inference``) for the poses of one test set, without its process / CLI
     shell: this rank's contiguous shard (DistributedEvalSampler arithmetic, EvaSampler.py:78-106) in batches of ``batch_size``
     with ``drop_last`` like the reference's DataLoader -> create_mask -> ``hypo`` completions -> de-normalise -> Evaler
@@ -148,7 +148,8 @@ def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs
     of (sum, count) pairs (``distributed.reduce_metric_means``) instead of ``gather_object`` of every value (:300-305).
     ``poses`` [N, D] normalised test poses (the dataset's ``poses`` tensor); returns ``({metric: mean}, samples evaluated here)``.
     ``solver``: "dposer" (the optimisation above, ``optimize_kwargs``) or one of the diffusion samplers "scoresde" | "mcg" | "dps"
-    (``solver_kwargs``: ``grad_step`` for MCG / DPS, ``eps``, ``denoise``, ``seed``); each hypothesis is one sampler call."""
+    (``solver_kwargs``: ``grad_step`` for MCG / DPS, ``eps``, ``denoise``, ``seed``); each hypothesis is one sampler call.
+    ``fused_eval``: score with ``Evaler.multi_eval_bodys(fused=True)`` -- one ``dposer_pose_pair_errors`` call per batch, no vertex tensors."""
     if solver not in SOLVERS:
         raise ValueError(f"unknown completion solver {solver!r}: expected one of {SOLVERS}")
     from .. import distributed as ddp
@@ -171,7 +172,7 @@ def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs
             outs = torch.stack([complete(observation, mask) for _ in range(hypo)], dim=1)
         preds = normalizer.offline_denormalize(outs, to_axis=True)
         gts = normalizer.offline_denormalize(batch, to_axis=True)
-        results.append(evaler.multi_eval_bodys(preds, gts, as_tensors=True))
+        results.append(evaler.multi_eval_bodys(preds, gts, as_tensors=True, fused=fused_eval))
         done += batch_size
     # fixed name list: a rank whose shard is shorter than one batch (drop_last) has no results to learn the names from
     return ddp.reduce_metric_means(results, device=dev, names=("mpjpe_body", "mpvpe_all")), done

@@ -71,12 +71,13 @@ def _to_axis(config, x):
     return x
 
 
-def validate(state, sde, config, test_poses, body_model, denormalize, out_dir=None, *, render=False, log=None, device=None):
+def validate(state, sde, config, test_poses, body_model, denormalize, out_dir=None, *, render=False, log=None, device=None,
+             fused_eval=False):
     """The validation block of train.py:263-372 under the EMA weights: per test batch of ``config.eval.batch_size`` poses the bpd
     (likelihood ODE, rtol = atol = eps = 1e-4), five sampler completions of the left leg scored by ``Evaler.multi_eval_bodys`` and one
     generation; then APD over the first 22 joints of the first 50 samples and ``last_samples.npz`` (``pose_trajs [10, 5, D_axis]``,
     ``pose_samples [1, 50, D_axis]``) in ``out_dir``.  ``render=True`` adds the OBJ / image files of :338-362.  The model's parameters
-    are restored and it is left in train mode.  Returns ``{'bpd', 'mpvpe_all', 'mpjpe_body', 'APD'}`` as floats."""
+    are restored and it is left in train mode.  ``fused_eval`` scores the completions with ``Evaler.multi_eval_bodys(fused=True)``.  Returns ``{'bpd', 'mpvpe_all', 'mpjpe_body', 'APD'}`` as floats."""
     model, ema = state["model"], state["ema"]
     device = torch.device(device) if device is not None else next(model.parameters()).device
     log = log or (lambda msg: None)
@@ -106,7 +107,7 @@ def validate(state, sde, config, test_poses, body_model, denormalize, out_dir=No
                                          for _ in range(HYPO_NUM)], dim=1)
                     preds = _to_axis(config, denormalize(hypos))
                     gts = _to_axis(config, denormalize(poses))
-                    res = evaler.multi_eval_bodys(preds, gts, as_tensors=True)
+                    res = evaler.multi_eval_bodys(preds, gts, as_tensors=True, fused=fused_eval)
                     metrics["mpvpe_all"].append(res["mpvpe_all"].mean())
                     metrics["mpjpe_body"].append(res["mpjpe_body"].mean())
                     trajs, samples = sampling_fn(model, observation=None)                  # task 3: generation, [t, b, D], [b, D]

@@ -114,6 +114,118 @@ def self_intersections_percentage_hip(vertices, faces):
     return counts / F * 100
 
 
+class IndexList:
+    """A vertex / joint-row list of ``pose_pair_errors`` checked on the host once: ``host`` (int32 numpy), its length ``n`` and largest
+    entry ``max``, and one int32 device copy per device (``on(device)``)."""
+
+    def __init__(self, idx, limit, name="index list"):
+        if isinstance(idx, torch.Tensor):
+            idx = idx.detach().cpu().numpy()
+        arr = np.asarray(idx)
+        if arr.ndim != 1 or arr.size < 1:
+            raise ValueError(f"{name} must be a non-empty 1-D list of indices, got shape {arr.shape}")
+        if not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"{name} must hold integers, got {arr.dtype}")
+        lo, hi = int(arr.min()), int(arr.max())
+        if lo < 0 or hi >= limit:
+            raise ValueError(f"{name} entries must lie in [0, {limit}), got [{lo}, {hi}]")
+        self.host = np.ascontiguousarray(arr, dtype=np.int32)
+        self.n, self.max, self.limit = int(arr.size), hi, int(limit)
+        self._dev = {}
+
+    def on(self, device):
+        key = str(device)
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.tensor(self.host, dtype=torch.int32, device=device)
+        return t
+
+
+def _as_index_list(idx, limit, name):
+    if idx is None:
+        return None
+    if isinstance(idx, IndexList):
+        if idx.limit != limit:
+            raise ValueError(f"{name} was checked against {idx.limit} entries, this body model has {limit}")
+        return idx
+    return IndexList(idx, limit, name)
+
+
+def _score_fronts(core, ref, hyp, hg, verts, rows, scale, min_into, mpvpe, mpjpe, mpvpe_h=None, mpjpe_h=None):
+    """One ``dposer_pose_pair_errors`` call on two ``lbs_front`` results: ``ref`` of B poses, ``hyp`` of B x ``hg`` (row b * hg + h)."""
+    from .. import _C
+    lib, h, dev, B = _C.lib(), core._handle(), mpvpe.device, ref.batch
+    n_list = verts.n if verts is not None else 0
+    scratch = torch.empty(lib.dposer_pose_pair_errors_scratch_bytes(h, B, hg, n_list), dtype=torch.uint8, device=dev)
+    a = _C.PosePairErrorsArgs(
+        body=h, ws_ref=ref.ws.data_ptr(), ws_hyp=hyp.ws.data_ptr(), joints_ref=ref.joints.data_ptr(), joints_hyp=hyp.joints.data_ptr(),
+        v_shaped=ref.v_shaped.data_ptr(), v_shaped_batched=1 if ref.batched else 0, skin_k=int(core.skin_idx.shape[1]),
+        skin_idx=core.skin_idx.data_ptr(), skin_w=core.skin_w.data_ptr(), transl_ref=None, transl_hyp=None,
+        vert_list=None if verts is None else verts.on(dev).data_ptr(), joint_rows=None if rows is None else rows.on(dev).data_ptr(),
+        num_listed_vertices=n_list, num_listed_rows=rows.n if rows is not None else 0, max_listed_row=rows.max if rows is not None else 0,
+        hypotheses=hg, extra_vertex_ids=core.extra_vertex_ids.data_ptr() if core.n_extra else None,
+        lmk_tri=core.lmk_tri.data_ptr() if core.n_lmk else None, lmk_bary=core.lmk_bary_coords.data_ptr() if core.n_lmk else None,
+        batch=B, scale=float(scale), min_into=1 if min_into else 0, mpvpe=mpvpe.data_ptr(), mpjpe=mpjpe.data_ptr(),
+        mpvpe_h=None if mpvpe_h is None else mpvpe_h.data_ptr(), mpjpe_h=None if mpjpe_h is None else mpjpe_h.data_ptr(), scratch=scratch.data_ptr())
+    _C.check(lib.dposer_pose_pair_errors(C.byref(a), _C.stream_ptr()), "dposer_pose_pair_errors")
+
+
+def pose_pair_errors(body_model, ref_pose_body, hyp_pose_body, *, vert_idx=None, joint_idx=None, scale=1.0, betas=None, per_hypothesis=False,
+                     max_workspace_bytes=1 << 30):
+    """MPVPE / MPJPE of hypothesis bodies against reference bodies, minimum over the hypotheses, without a vertex tensor
+    (``dposer_pose_pair_errors``; the rule is written out in include/dposer_hip.h).
+
+    ``ref_pose_body [B, 63]``, ``hyp_pose_body [B, 63]`` or ``[B, H, 63]`` axis-angle body poses on a ROCm device; ``betas [B, nb]``
+    per sample (shared by its hypotheses) or None.  ``vert_idx`` / ``joint_idx``: the vertices and the rows of the LBS joint output to
+    average over (None = all) -- host indices (list, numpy, CPU tensor) or an ``IndexList``; they are range-checked on the host, so pass an
+    ``IndexList`` built once to keep a device-resident list from being copied back.  ``scale``: 1000 for millimetres.
+    Returns ``{"mpvpe": [B], "mpjpe": [B]}`` (+ ``"mpvpe_h"``, ``"mpjpe_h"`` ``[B, H]`` with ``per_hypothesis``) as device tensors.
+    One front call (FK + pose-blend offsets) for the references, one per group of hypotheses whose front workspace fits
+    ``max_workspace_bytes``; later groups fold into the minimum on the device.  Never synchronises with the host."""
+    from .. import _C
+    core = getattr(body_model, "bm", body_model)
+    n_rows = core.J + core.n_extra + core.n_lmk
+    verts = _as_index_list(vert_idx, core.V, "vert_idx")          # (host checks first: they need no device)
+    rows = _as_index_list(joint_idx, n_rows, "joint_idx")
+    _C.require_gpu(ref_pose_body, "ref_pose_body")
+    _C.require_gpu(hyp_pose_body, "hyp_pose_body")
+    if hyp_pose_body.dim() == 2:
+        hyp_pose_body = hyp_pose_body[:, None]
+    if ref_pose_body.dim() != 2 or hyp_pose_body.dim() != 3 or hyp_pose_body.shape[0] != ref_pose_body.shape[0] or \
+            hyp_pose_body.shape[2] != ref_pose_body.shape[1]:
+        raise ValueError(f"expected ref [B, D] and hyp [B, D] or [B, H, D], got {tuple(ref_pose_body.shape)} and {tuple(hyp_pose_body.shape)}")
+    B, H = int(hyp_pose_body.shape[0]), int(hyp_pose_body.shape[1])
+    if B < 1 or H < 1:
+        raise ValueError("pose_pair_errors needs at least one sample and one hypothesis")
+    dev = ref_pose_body.device
+    lib, h = _C.lib(), core._handle()
+    with torch.no_grad():
+        rest = core.rest_shape(betas, None)
+        ref = core.lbs_front(rest=rest, body_pose=ref_pose_body)
+        # hypotheses per front call: the most whose workspace fits the budget
+        group = H
+        while group > 1 and lib.dposer_lbs_workspace_bytes(h, B * group) > max_workspace_bytes:
+            group -= 1
+        rest_h = rest
+        out = {"mpvpe": torch.empty(B, dtype=torch.float32, device=dev), "mpjpe": torch.empty(B, dtype=torch.float32, device=dev)}
+        per = {"mpvpe_h": [], "mpjpe_h": []}
+        for g0 in range(0, H, group):
+            hg = min(group, H - g0)
+            if rest[2]:                                      # per-sample rest joints, one row per (sample, hypothesis)
+                rest_h = (rest[0], rest[1].repeat_interleave(hg, dim=0), True)
+            hyp = core.lbs_front(rest=rest_h, body_pose=hyp_pose_body[:, g0:g0 + hg].reshape(B * hg, -1))
+            vh = torch.empty(B, hg, dtype=torch.float32, device=dev) if per_hypothesis else None
+            jh = torch.empty(B, hg, dtype=torch.float32, device=dev) if per_hypothesis else None
+            _score_fronts(core, ref, hyp, hg, verts, rows, scale, g0 > 0, out["mpvpe"], out["mpjpe"], vh, jh)
+            hyp = None                                       # (the next group's workspace takes this one's place, not a third)
+            if per_hypothesis:
+                per["mpvpe_h"].append(vh)
+                per["mpjpe_h"].append(jh)
+        if per_hypothesis:
+            out.update({k: v[0] if len(v) == 1 else torch.cat(v, dim=1) for k, v in per.items()})
+    return out
+
+
 def generation_metrics(body_out):
     """{"APD", "SI"} of demo.py:148-161 from ``BodyModel.forward``'s output (dict or attribute struct): APD over the first 22 joints,
     SI as the mean over the meshes of ``self_intersections_percentage_hip``."""

@@ -559,6 +559,74 @@ int dposer_lbs_backward_temporal(dposer_body_t h, const void* ws_fwd, void* ws_b
                                  float* dist_part4, const float* d_joints, int64_t d_joints_ld, float* const* d_pose_segments_host,
                                  int64_t batch, void* stream);
 
+/* Pose-pair errors -- Evaler.eval_bodys / multi_eval_bodys of lib/dataset/AMASS.py:275-316 for `batch` samples, each one reference
+ * body and `hypotheses` hypothesis bodies, in one call: MPVPE (mean per-vertex position error) and MPJPE (mean per-joint position
+ * error) per hypothesis and their minimum over the hypotheses.  No vertex array exists in memory: both bodies are skinned in registers
+ * from the workspaces two dposer_lbs_forward_front calls left behind.
+ * Inputs:
+ *   ws_ref / joints_ref: workspace and joints [batch, J + num_extra + num_landmarks, 3] of the front call over the `batch` reference poses
+ *   (only joints[:, :J] is valid, as that call leaves it);  ws_hyp / joints_hyp: the same of ONE front call over batch * hypotheses poses,
+ *   hypothesis h of sample b at row b * hypotheses + h.  Both workspaces unmodified since.
+ *   v_shaped [V,3] (shared) or [batch,V,3] (sample b's, shared by its hypotheses); skin_idx / skin_w / skin_k as dposer_lbs_forward;
+ *   transl_ref [batch,3] / transl_hyp [batch * hypotheses,3] or NULL: the translations the two front calls were given;
+ *   vert_list [num_listed_vertices] int32 or NULL (= all V vertices); joint_rows [num_listed_rows] int32 (at most 4096) or NULL (= all
+ *   J + num_extra + num_landmarks rows of the LBS joint output); max_listed_row: the largest entry of joint_rows (ignored when it is NULL);
+ *   extra_vertex_ids / lmk_tri / lmk_bary as dposer_lbs_forward: required when max_listed_row reaches the rows they produce.
+ *   The lists are device arrays and are NOT range-checked: the caller guarantees 0 <= vert_list[i] < V and
+ *   0 <= joint_rows[i] <= max_listed_row < J + num_extra + num_landmarks.
+ * Rule, for sample b and hypothesis h:
+ *   mpvpe_h[b,h] = scale * (sum over listed vertices of ||v_hyp - v_ref||) / num_listed_vertices.  Both vertices are formed exactly as
+ *   dposer_lbs_forward forms them: p = v_shaped + offsets, T = sum_k w_k A[j_k], v = T [p ; 1] + transl, the blend and the product
+ *   contracted to FMAs as in its skinning kernels.  Differences, squares, their sum x^2 + y^2 + z^2 (left to right), the square root
+ *   (correctly rounded), the sums, the division and the scaling are fp32 without contraction.
+ *   mpjpe_h[b,h] is the same over the listed joint rows: a row < J is read from the two joint arrays; a row in [J, J + num_extra) is the
+ *   skinned vertex extra_vertex_ids[row - J] of either body; a landmark row l is ((0 + v_0 w_0) + v_1 w_1) + v_2 w_2 over the skinned
+ *   vertices lmk_tri[l] with weights lmk_bary[l], per coordinate (dposer_lbs_forward's landmark sum).
+ *   mpvpe[b] = min_h mpvpe_h[b,h], mpjpe[b] = min_h mpjpe_h[b,h]; a NaN value makes the minimum NaN (torch.min).  min_into = 0 writes
+ *   mpvpe / mpjpe; min_into = 1 takes the minimum of the new values and what the two arrays already hold (a NaN on either side
+ *   stays): hypotheses can be scored in several calls against a bounded workspace.
+ * Summation order: the vertex distances of a 256-entry block of the list are added by xor butterfly inside each of four 64-lane waves,
+ *   the four waves as ((p0 + p1) + p2) + p3, the blocks in list order; the joint distances by 128 strided per-thread sums, a butterfly per
+ *   wave, then wave 0 + wave 1.  No atomics.  The order depends on the list lengths alone: a sample's outputs are a function of its own
+ *   data, whatever the batch, its position in it, the number of hypotheses or their split into calls.
+ * Outputs: mpvpe [batch], mpjpe [batch]; mpvpe_h / mpjpe_h [batch, hypotheses] or NULL.
+ * scratch: dposer_pose_pair_errors_scratch_bytes(body, batch, hypotheses, listed_vertices) bytes (listed_vertices <= 0: all vertices),
+ *   256-byte aligned.  Queues two kernels on the stream; allocates nothing, never synchronises the host.
+ * Layout (LP64): pointers and int64 at 8-byte alignment, int32 / float at 4; sizeof = 200. */
+typedef struct dposer_pose_pair_errors_args {
+    dposer_body_t body;               /*   0 */
+    const void* ws_ref;               /*   8 */
+    const void* ws_hyp;               /*  16 */
+    const float* joints_ref;          /*  24 */
+    const float* joints_hyp;          /*  32 */
+    const float* v_shaped;            /*  40 */
+    int32_t v_shaped_batched;         /*  48 */
+    int32_t skin_k;                   /*  52 */
+    const int32_t* skin_idx;          /*  56 */
+    const float* skin_w;              /*  64 */
+    const float* transl_ref;          /*  72 */
+    const float* transl_hyp;          /*  80 */
+    const int32_t* vert_list;         /*  88 */
+    const int32_t* joint_rows;        /*  96 */
+    int32_t num_listed_vertices;      /* 104 */
+    int32_t num_listed_rows;          /* 108 */
+    int32_t max_listed_row;           /* 112 */
+    int32_t hypotheses;               /* 116 */
+    const int32_t* extra_vertex_ids;  /* 120 */
+    const int32_t* lmk_tri;           /* 128 */
+    const float* lmk_bary;            /* 136 */
+    int64_t batch;                    /* 144 */
+    float scale;                      /* 152: 1000 = millimetres, 100 = centimetres for bodies in metres */
+    int32_t min_into;                 /* 156 */
+    float* mpvpe;                     /* 160 */
+    float* mpjpe;                     /* 168 */
+    float* mpvpe_h;                   /* 176 */
+    float* mpjpe_h;                   /* 184 */
+    void* scratch;                    /* 192 */
+} dposer_pose_pair_errors_args;
+int64_t dposer_pose_pair_errors_scratch_bytes(dposer_body_t h, int64_t batch, int32_t hypotheses, int32_t listed_vertices);
+int dposer_pose_pair_errors(const dposer_pose_pair_errors_args* args, void* stream);
+
 /* Backward of dposer_lbs_forward (autograd of BodyModel.forward w.r.t. pose / rest joints / v_posed; the reference
  * differentiates through smplx in run/motion_denoising.py:217-218,255-267 and run/smplify.py:200-260).
  *   ws_fwd: the workspace of the matching forward call (unmodified since);  posedirs_bwd_packed:
