@@ -607,8 +607,11 @@ def test_train_steps_match_reference_golden(prec):
     assert ema.num_updates == 5
 
 
-@pytest.mark.parametrize("prec", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16x3"])
 def test_autograd_forward_backward_vs_oracle(prec):
+    # bf16: the file's bf16 bounds -- TOL_BF16 forward, 2e-2 for a gradient through the network (measured 4.7e-3 forward, 7.1e-3 x.grad, at most 7.3e-3 a parameter);
+    # tests/test_gpu_bf16_faithful.py holds the same path row by row to the rounding-faithful oracle
+    tol_out, tol_dx, tol_dw = (TOL_BF16, 2e-2, 2e-2) if prec == "bf16" else (TOL_FP32, 2e-4, 3e-4)
     cfg, m, p = make_model(41, precision=prec, dropout=0.0)
     B = 50
     rs = np.random.RandomState(2)
@@ -625,13 +628,13 @@ def test_autograd_forward_backward_vs_oracle(prec):
     xr = torch.tensor(x, requires_grad=True)
     ref = R.scorefc_forward(full, xr, torch.tensor(t) * 999)
     grads = torch.autograd.grad((ref * torch.tensor(w)).sum(), [xr] + [leaves[n] for n in names], allow_unused=True)
-    assert rel_err(t2n(out), ref.detach().numpy()) < TOL_FP32
-    assert rel_err(t2n(xd.grad), grads[0].numpy()) < 2e-4
+    assert rel_err(t2n(out), ref.detach().numpy()) < tol_out
+    assert rel_err(t2n(xd.grad), grads[0].numpy()) < tol_dx
     for (n, prm), gr in zip(m.named_parameters(), grads[1:]):
         if gr is None:
             assert prm.grad is None
             continue
-        assert rel_err(t2n(prm.grad), gr.numpy()) < 3e-4, n
+        assert rel_err(t2n(prm.grad), gr.numpy()) < tol_dw, n
 
 
 def test_full_batch_train_step_properties():
