@@ -156,6 +156,71 @@ __global__ void __launch_bounds__(256) k_md_joint(const float* joints, int64_t l
     }
 }
 
+// the data term of PARTIAL observations (joints_conf and / or obs_rows given; the rule is written out at dposer_motion_denoise_args):
+// column j of the observation is tree joint rows[j] (NULL: j) with confidence conf[t, j] (NULL: 1); an entry is live iff its
+// confidence is > 0 (false for 0, negatives and NaN), and a dead entry's observation never enters a sum -- it may be NaN.  data = sum_live
+// c ||r|| / sum_live c, kept iff the weight sum is > 0 and the value is finite and > 0.  Same two passes, the same clamp, the same
+// fixed-order block sums and the same two log forms as k_md_joint; with c = 1 and rows = 0 .. n_obs - 1 every sum, the decision and every
+// gradient row carry k_md_joint's bits (the weight sum is then the entry count, exactly).  A row outside [0, n_rows) is never
+// dereferenced: its column counts as dead.
+// CONF / ROWS: which of the two arrays exist -- compile-time, so that the loops hold no branch that merges paths with and without a
+// load in flight (the compiler then waits for every outstanding load, vmcnt(0), before it issues the next; measured: 12.7 vs 9.9 us for
+// k_md_joint at one block of 60 x 22 entries, profiles/md_partial_time.md).
+template <bool CONF, bool ROWS> __global__ void __launch_bounds__(256) k_md_joint_obs(const float* joints, int64_t ld, const float* obs, const float* conf, const int32_t* rows, int n_rows,
+                                                      float* djoints, int T, int n_obs, float w_data, const float* temp_part, int n_temp_part,
+                                                      float temp_scale, const float* prior_loss, float* log3) {
+    __shared__ float red[4];
+    // block = one sequence of T frames
+    joints += (int64_t)blockIdx.x * T * ld; djoints += (int64_t)blockIdx.x * T * ld; obs += (int64_t)blockIdx.x * T * n_obs * 3;
+    if (CONF) conf += (int64_t)blockIdx.x * T * n_obs;
+    temp_part += (int64_t)blockIdx.x * n_temp_part;
+    if (log3) log3 += 3 * (int64_t)blockIdx.x;
+    const int n = T * n_obs;
+    float acc = 0.f, wacc = 0.f;
+    for (int e = threadIdx.x; e < n; e += 256) {
+        const int t = e / n_obs, j = e % n_obs;
+        const int row = ROWS ? rows[j] : j;
+        const bool in_range = (unsigned)row < (unsigned)n_rows;
+        // (the distance is formed for every entry and DISCARDED by a select for a dead one: behind a branch on the confidence, the joint and
+        //  observation loads wait for the confidence load first -- two memory latencies per trip of a latency-bound block,
+        //  profiles/md_partial_time.md)
+        const float c = CONF ? conf[e] : 1.0f;
+        const float* a = joints + (int64_t)t * ld + (in_range ? row : 0) * 3;
+        const float* o = obs + (int64_t)e * 3;
+        const float dx = a[0] - o[0], dy = a[1] - o[1], dz = a[2] - o[2];
+        const float s = dx * dx + dy * dy + dz * dz;
+        const float d = sqrtf(s < 1e-36f ? 1e-36f : s);      // (a NaN is not clamped: a NaN under a positive confidence drops the term, as in k_md_joint)
+        const bool live = c > 0.f && in_range;
+        const float cl = live ? c : 0.f;
+        acc += cl * (live ? d : 0.f);                        // (+ 0 for a dead entry, never 0 x NaN)
+        wacc += cl;
+    }
+    const float wsum = block_sum(wacc, red);
+    const float data = block_sum(acc, red) / wsum;      // (0 / 0 = NaN for a sequence without a live entry: dropped below)
+    const bool keep = wsum > 0.f && isfinite(data) && data > 0.f;
+    const float g = keep ? w_data / wsum : 0.f;
+    for (int e = threadIdx.x; e < n; e += 256) {
+        const int t = e / n_obs, j = e % n_obs;
+        const int row = ROWS ? rows[j] : j;
+        if ((unsigned)row >= (unsigned)n_rows) continue;
+        const float c = CONF ? conf[e] : 1.0f;
+        const float* a = joints + (int64_t)t * ld + row * 3;
+        const float* o = obs + (int64_t)e * 3;
+        const float dx = a[0] - o[0], dy = a[1] - o[1], dz = a[2] - o[2];
+        const float s = dx * dx + dy * dy + dz * dz;
+        float* dj = djoints + (int64_t)t * ld + row * 3;
+        const bool live = c > 0.f && s > 1e-36f;      // (false for a dead entry whatever its residual, and for a NaN residual)
+        const float d = sqrtf(s), gc = g * c;
+        dj[0] = live ? gc * (dx / d) : 0.f; dj[1] = live ? gc * (dy / d) : 0.f; dj[2] = live ? gc * (dz / d) : 0.f;
+    }
+    if (log3) {
+        float tp = 0.f;
+        for (int i = threadIdx.x; i < n_temp_part; i += 256) tp += temp_part[i];
+        const float temp = block_sum(tp, red) * temp_scale;
+        if (threadIdx.x == 0) { log3[0] = temp; log3[1] = keep ? data : 0.f; log3[2] = prior_loss[0]; }
+    }
+}
+
 // log3[0] of a step whose temporal term is formed inside the skinning backward (dposer_lbs_backward_temporal): the per-wave distance sums
 // [frames][vb][4] arrive behind that kernel; ((p0 + p1) + p2) + p3 of an entry is k_md_vert_grad's block sum, the rest is k_md_joint's sum
 __global__ void __launch_bounds__(256) k_md_temp_log(const float* part4, int n_temp_part, float temp_scale, float* log3) {
@@ -352,6 +417,13 @@ extern "C" int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* 
             else hipLaunchKernelGGL(k_md_vert_grad<false>, dim3((unsigned)vb, (unsigned)T), dim3(256), 0, st, (const float*)s.verts, s.dverts, s.part, (int)F, V, c_temp);
             TK_HIP_LAUNCH(hipGetLastError());
         }
+        if (a->joints_conf || a->obs_rows) {      // partial observations: confidences and / or a joint list (neither: the kernel and the bits of every call before them)
+            auto kern = a->joints_conf ? (a->obs_rows ? k_md_joint_obs<true, true> : k_md_joint_obs<true, false>) : k_md_joint_obs<false, true>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_seq), dim3(256), 0, st, (const float*)s.joints, (int64_t)a->joint_rows * 3, a->joints_obs,
+                               a->joints_conf, a->obs_rows, a->num_joints, s.djoints, (int)F, a->n_obs_joints, a->w_data_host[k], (const float*)s.part,
+                               temporal_in_backward ? 0 : vb * (int)F, 1.0f / ((float)(F - 1) * (float)V), (const float*)s.loss1,
+                               a->loss_log ? a->loss_log + 3 * (int64_t)k * n_seq : nullptr);
+        } else
         hipLaunchKernelGGL(k_md_joint, dim3((unsigned)n_seq), dim3(256), 0, st, (const float*)s.joints, (int64_t)a->joint_rows * 3, a->joints_obs, s.djoints,
                            (int)F, a->n_obs_joints, a->w_data_host[k], (const float*)s.part, temporal_in_backward ? 0 : vb * (int)F,
                            1.0f / ((float)(F - 1) * (float)V), (const float*)s.loss1, a->loss_log ? a->loss_log + 3 * (int64_t)k * n_seq : nullptr);

@@ -51,6 +51,27 @@ def create_mask(body_poses, part="legs", observation_type="noise"):
     return mask, observation
 
 
+def occlude_joints(joints3d, part=None, joints=None):
+    """Partial 3D observations for ``MotionDenoise`` (``joints_conf=``): ``joints3d`` [..., n, 3] tree joints ->
+    (the joints with NaN at the occluded ones, confidence [..., n]: 0 there and 1 elsewhere).  ``part``: a ``BodyPartIndices`` name --
+    pose index i rotates tree joint i + 1 (the pelvis is joint 0), so 'left_leg' occludes joints 1, 4, 7, 10; ``joints``: tree-joint
+    indices, occluded as well."""
+    if part is None and joints is None:
+        raise ValueError("occlude_joints: give a body part, a joint list or both")
+    idx = set() if joints is None else {int(j) for j in joints}
+    if part is not None:
+        idx |= {int(i) + 1 for i in getattr(BodyPartIndices, part)}
+    n = joints3d.shape[-2]
+    if any(j < 0 or j >= n for j in idx):
+        raise ValueError(f"occlude_joints: joints {sorted(idx)} outside the {n} observed ones")
+    idx = torch.tensor(sorted(idx), dtype=torch.long, device=joints3d.device)
+    out = joints3d.clone()
+    out[..., idx, :] = float("nan")
+    conf = torch.ones(joints3d.shape[:-1], dtype=joints3d.dtype, device=joints3d.device)
+    conf[..., idx] = 0.0
+    return out, conf
+
+
 def linear_interpolation(A, B, frames):
     alpha = torch.linspace(0, 1, frames, device=A.device)[:, None]
     return (1 - alpha) * A + alpha * B

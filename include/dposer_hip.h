@@ -701,7 +701,24 @@ int dposer_lbs_backward(dposer_body_t h, const void* ws_fwd, void* ws_bwd, const
  *   (independent problems advanced together: temporal neighbours, the data-term decision and the loss means are per sequence; the
  *   in-kernel prior noise is keyed by the frame index inside the batch);
  *   loss_log: DEVICE [n_steps, sequences, 3] (temp, data values of each sequence; the prior value is the batch total, i.e. the sum
- *   over the sequences' prior terms) of every step, unweighted, or NULL. */
+ *   over the sequences' prior terms) of every step, unweighted, or NULL.
+ *
+ * PARTIAL OBSERVATIONS (joints_conf and / or obs_rows, the last two fields; both NULL = everything above, kernel for kernel and bit
+ * for bit).  For one sequence of F frames, with observed columns j = 0 .. n_obs_joints - 1 of joints_obs [frames, n_obs_joints, 3]:
+ *   rows[j] = obs_rows[j] is the tree joint column j observes (obs_rows == NULL: rows[j] = j).  The entries are distinct and lie in
+ *     [0, num_joints) -- tree joints only: dposer_lbs_backward_temporal ignores gradient rows >= num_joints.  (The caller checks this;
+ *     the kernel never dereferences a row outside that range -- its column counts as not live.)
+ *   c = joints_conf[t, j], float32 [frames, n_obs_joints] (joints_conf == NULL: c = 1).
+ *   An entry (t, j) is LIVE iff c > 0 -- false for 0, for negatives and for NaN.
+ *   For an entry that is not live, joints_obs[t, j] never enters any sum and may be NaN or Inf; its gradient row is written as 0.
+ *   r = J[t, rows[j]] - joints_obs[t, j],  s2 = |r|^2.
+ *   W = sum_live c,  N = sum_live c * sqrt(s2 < 1e-36 ? 1e-36 : s2)  (a NaN s2 is not clamped),  data = N / W.
+ *   The term is KEPT iff W > 0 and data is finite and data > 0.
+ *   d data / d J[t, rows[j]] = w_data * (c / W) * r / sqrt(s2) for the live entries of a kept term with s2 > 1e-36, else 0.
+ *   loss_log column 1 holds data when kept and 0 when dropped.
+ * Consequences: a sequence with NO live entry (W = 0) keeps moving under the prior and the temporal term alone; a NaN observation under a
+ * POSITIVE confidence makes N NaN and drops that sequence's term for the step, exactly as without confidences.  W, N and the decision are
+ * per sequence; the sums are fp32 block sums in a fixed order (no atomics), so a call is reproducible bit for bit. */
 typedef struct dposer_motion_denoise_args {
     dposer_scorefc_t net;
     const float* flat_params;
@@ -759,6 +776,8 @@ typedef struct dposer_motion_denoise_args {
     float* loss_log;
     int32_t rot6d;        /* != 0: the score network works on the 6-D rotation representation (rot_rep = 'rot6d': 6 J inputs, norm_a / norm_b
                              hold 6 J statistics, noise is [n_steps, frames, 6 J]); the pose being optimised stays axis-angle */
+    const float* joints_conf;     /* DEVICE [frames, n_obs_joints] confidences of PARTIAL OBSERVATIONS above, or NULL = 1 everywhere */
+    const int32_t* obs_rows;      /* DEVICE [n_obs_joints] distinct tree joints in [0, num_joints) the columns observe, or NULL = 0 .. n_obs_joints - 1 */
 } dposer_motion_denoise_args;
 int64_t dposer_motion_denoise_scratch_bytes(int64_t frames, int32_t pose_dim, int32_t num_vertices, int32_t joint_rows);
 int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* args, void* stream);
