@@ -600,10 +600,7 @@ __global__ void __launch_bounds__(256) k_completion_update(WithSde<CompletionUpd
         const float g_data = (((2.0f * (x * mk - a.obs[i] * mk)) * a.inv_n) * a.w_data) * mk;
         const float g = g_prior + g_data;
         float m = a.m[i], v = a.v[i];
-        m = m + (g - m) * a.one_minus_beta1;                          // exp_avg.lerp_(grad, 1 - beta1)
-        v = v * a.beta2 + a.one_minus_beta2 * (g * g);                // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
-        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-        x = x - a.step_size * (m / denom);                            // param.addcdiv_(exp_avg, denom, value=-step_size)
+        x = adam_step(x, g, m, v, a.s);
         a.m[i] = m;
         a.v[i] = v;
         a.x[i] = x;
@@ -1503,10 +1500,7 @@ __device__ __forceinline__ float adam_math(const AdamArgs& a, float coef, bool s
     if (!skip) {
         g = g * coef;
         if (a.weight_decay != 0.f) g = g + a.weight_decay * p;   // torch.optim.Adam: grad = grad.add(param, alpha=weight_decay)
-        m = m + (g - m) * a.one_minus_beta1;                      // exp_avg.lerp_(grad, 1 - beta1)
-        v = v * a.beta2 + a.one_minus_beta2 * (g * g);            // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
-        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-        p = p - a.step_size * (m / denom);                        // param.addcdiv_(exp_avg, denom, value=-step_size)
+        p = adam_step(p, g, m, v, a.s);
     }
     s = s - a.ema_one_minus_decay * (s - p);                      // ema.py:51  s -= (1 - decay) * (s - p)
     return p;

@@ -25,13 +25,6 @@
 
 #pragma clang fp contract(off)
 
-#define FK_HIP_LAUNCH(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return dposer_set_error(DPOSER_ERR_HIP, std::string(__func__) + ": " + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------------
 // LDS-transposed streaming: a block of NT lanes owns NT consecutive items of IN / OUT floats.
 // ------------------------------------------------------------------------------------------------
@@ -166,7 +159,7 @@ extern "C" int dposer_rotmat_to_axis_angle(const float* rotmat, float* axis_angl
     DP_CHECK_ARG(rotmat && axis_angle && n >= 0, "bad argument");
     if (n == 0) return DPOSER_OK;
     hipLaunchKernelGGL(k_to_axis_angle<false>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, rotmat, axis_angle, n);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 extern "C" int dposer_rot6d_to_axis_angle(const float* rot6d, float* axis_angle, int64_t n, void* stream) {
@@ -174,7 +167,7 @@ extern "C" int dposer_rot6d_to_axis_angle(const float* rot6d, float* axis_angle,
     DP_CHECK_ARG(rot6d && axis_angle && n >= 0, "bad argument");
     if (n == 0) return DPOSER_OK;
     hipLaunchKernelGGL(k_to_axis_angle<true>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, rot6d, axis_angle, n);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 
@@ -183,7 +176,7 @@ extern "C" int dposer_rodrigues(const float* aa, float* rotmat, int64_t n, void*
     DP_CHECK_ARG(aa && rotmat && n >= 0, "bad argument");
     if (n == 0) return DPOSER_OK;
     hipLaunchKernelGGL(k_rodrigues, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, aa, rotmat, n);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 extern "C" int dposer_rot6d_to_rotmat(const float* rot6d, float* rotmat, int64_t n, void* stream) {
@@ -191,7 +184,7 @@ extern "C" int dposer_rot6d_to_rotmat(const float* rot6d, float* rotmat, int64_t
     DP_CHECK_ARG(rot6d && rotmat && n >= 0, "bad argument");
     if (n == 0) return DPOSER_OK;
     hipLaunchKernelGGL(k_rot6d, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, rot6d, rotmat, n);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 
@@ -291,7 +284,7 @@ extern "C" int dposer_shape_blend_forward(const float* v_template, const float* 
     DP_CHECK_ARG(ceil_div(batch, SB_POSES) <= 65535, "batch too large for one launch");
     hipLaunchKernelGGL(k_shape_blend, dim3(v_tiles + j_tiles, (unsigned)ceil_div(batch, SB_POSES)), dim3(256), 0, (hipStream_t)stream, v_template,
                        shapedirs, j_template, jdirs, shape, v_shaped, j_rest, V3, J3, num_shape, batch, v_tiles);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 extern "C" int64_t dposer_shape_blend_scratch_floats(int32_t num_vertices, int32_t num_shape, int64_t batch) {
@@ -309,10 +302,10 @@ extern "C" int dposer_shape_blend_backward(const float* shapedirs, const float* 
     const int n_chunks = (int)ceil_div(V3, SBB_CHUNK);
     hipLaunchKernelGGL(k_shape_blend_bwd_part, dim3(n_chunks, (unsigned)batch, (unsigned)ceil_div(num_shape, SB_L)), dim3(256), 0, (hipStream_t)stream, shapedirs, d_v_shaped, scratch, V3,
                        num_shape, n_chunks);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_shape_blend_bwd_final, dim3((unsigned)ceil_div(batch * num_shape, 128)), dim3(128), 0, (hipStream_t)stream, scratch, jdirs,
                        d_j_rest, d_shape, J3, num_shape, n_chunks, batch);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 
@@ -887,9 +880,9 @@ extern "C" int dposer_fk_joints(dposer_body_t h, const float* const* pose_segmen
     a.nseg = num_segments; a.j_rest = j_rest; a.j_rest_batched = j_rest_batched; a.transl = transl; a.joints = joints;
     a.rel = rel_transforms; a.n_out = n_out; a.B = batch; a.joints_ld = (int64_t)n_out * 3;
     hipStream_t st = (hipStream_t)stream;
-    if (h->kind == 0) FK_HIP_LAUNCH(launch_fk<KinSMPL>(a, st));
-    else if (h->kind == 1) FK_HIP_LAUNCH(launch_fk<KinSMPLH>(a, st));
-    else FK_HIP_LAUNCH(launch_fk<KinSMPLX>(a, st));
+    if (h->kind == 0) DP_CHECK_HIP(launch_fk<KinSMPL>(a, st));
+    else if (h->kind == 1) DP_CHECK_HIP(launch_fk<KinSMPLH>(a, st));
+    else DP_CHECK_HIP(launch_fk<KinSMPLX>(a, st));
     return DPOSER_OK;
 }
 
@@ -1228,7 +1221,7 @@ extern "C" int dposer_lbs_pack_posedirs(dposer_body_t h, const float* posedirs, 
     js.n = 3;
     js.job[1] = j; js.job[1].dst_off = n * 4; js.job[1].f32 = 0; js.job[1].split = 1;
     js.job[2] = j; js.job[2].dst_off = n * 6; js.job[2].f32 = 0; js.job[2].split = 2;
-    FK_HIP_LAUNCH(launch_pack(js, posedirs, packed, (hipStream_t)stream));
+    DP_CHECK_HIP(launch_pack(js, posedirs, packed, (hipStream_t)stream));
     return DPOSER_OK;
 }
 // The forward workspace of `batch` poses, as byte offsets from its base: the ONE place its layout is written (the front half fills it;
@@ -1286,16 +1279,16 @@ static int lbs_forward_front(dposer_body_t h, void* ws, const void* posedirs_pac
     DP_CHECK_ARG(first == J, "pose segments must cover all joints of the kinematic tree");
     a.nseg = num_segments; a.j_rest = j_rest; a.j_rest_batched = j_rest_batched; a.transl = transl; a.joints = joints;
     a.joints_ld = (int64_t)n_total * 3; a.rel = A; a.pf = pf; a.pf_K = Ppad; a.n_out = J; a.B = batch;
-    if (h->kind == 0) FK_HIP_LAUNCH(launch_fk<KinSMPL>(a, st));
-    else if (h->kind == 1) FK_HIP_LAUNCH(launch_fk<KinSMPLH>(a, st));
-    else FK_HIP_LAUNCH(launch_fk<KinSMPLX>(a, st));
+    if (h->kind == 0) DP_CHECK_HIP(launch_fk<KinSMPL>(a, st));
+    else if (h->kind == 1) DP_CHECK_HIP(launch_fk<KinSMPLH>(a, st));
+    else DP_CHECK_HIP(launch_fk<KinSMPLX>(a, st));
 
     // 2. pose-blend offsets[b][3V] = pose_feature @ posedirs: rows = poses, lanes = vertex coords
     int Keff = body_tuning().lbs_k_prefix ? (int)round_up(lbs_posed_cols(pose_segments_host, segment_joints_host, num_segments, J), 32) : Ppad;
     Keff = Keff < 32 ? 32 : (Keff > Ppad ? Ppad : Keff);       // K prefix: the columns of the joints that are posed, in whole 32-column stages, at least one
     if (!lbs_blend_fp32()) {
         hipLaunchKernelGGL(k_split_pf, dim3((unsigned)ceil_div(Bpad * (Keff / 8), 256)), dim3(256), 0, st, (const float*)pf, pf_split, Bpad, Ppad, Keff);
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     GemmArgs g;
     std::memset(&g, 0, sizeof(g));
@@ -1305,7 +1298,7 @@ static int lbs_forward_front(dposer_body_t h, void* ws, const void* posedirs_pac
     if (lbs_blend_fp32()) {
         g.W = pf; g.w_stride_blocks = Ppad / 8; g.n_cblk = (int)(Bpad / 128); g.n_sblk = (int)(Cpad / 128);
         g.src[0] = posedirs_packed; g.seg_kblocks[0] = Keff / 8; g.seg_stride_blocks[0] = Ppad / 8; g.nseg = 1; g.ktot_blocks = Keff / 8;
-        FK_HIP_LAUNCH(gemm_wgrad(PREC_FP32, SHAPE_MID, g, wp, st));
+        DP_CHECK_HIP(gemm_wgrad(PREC_FP32, SHAPE_MID, g, wp, st));
     } else {
         const char* hi = (const char*)posedirs_packed + Cpad * Ppad * 4;
         const char* lo = hi + Cpad * Ppad * 2;
@@ -1316,7 +1309,7 @@ static int lbs_forward_front(dposer_body_t h, void* ws, const void* posedirs_pac
         g.src[0] = hi; g.src[1] = lo; g.src[2] = hi;                        // [pf_hi | pf_hi | pf_lo] x [hi ; lo ; hi]
         g.seg_kblocks[0] = g.seg_kblocks[1] = g.seg_kblocks[2] = kbe; g.nseg = 3; g.ktot_blocks = 3 * kbe;
         g.seg_stride_blocks[0] = g.seg_stride_blocks[1] = g.seg_stride_blocks[2] = kb;      // (rows of the packed posedirs keep their full width)
-        FK_HIP_LAUNCH(gemm_wgrad(PREC_BF16, shape, g, wp, st));
+        DP_CHECK_HIP(gemm_wgrad(PREC_BF16, shape, g, wp, st));
     }
     *A_out = A;
     *offsets_out = offsets;
@@ -1353,7 +1346,7 @@ extern "C" int dposer_lbs_forward(dposer_body_t h, void* ws, const void* posedir
             hipLaunchKernelGGL(k_skin_run, dim3(grid.x, (unsigned)ceil_div(nb, run)), dim3(256), 2 * J * 12 * sizeof(float), ss, s, run, (int64_t)nb);
         } else if (mode != 0 && skin_k == 4) hipLaunchKernelGGL(k_skin_x4, grid, dim3(256), J * 12 * sizeof(float), ss, s);
         else hipLaunchKernelGGL(k_skin, grid, dim3(256), J * 12 * sizeof(float), ss, s);
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
         return DPOSER_OK;
     };
     DP_TRY(skin(0, batch, st));
@@ -1366,7 +1359,7 @@ extern "C" int dposer_lbs_forward(dposer_body_t h, void* ws, const void* posedir
         e.ld = (int64_t)n_total * 3; e.J = J; e.n_extra = h->d.num_extra; e.n_lmk = h->d.num_landmarks; e.V = V; e.B = batch;
         const int64_t total = batch * (e.n_extra + e.n_lmk);
         hipLaunchKernelGGL(k_extra_joints, dim3((unsigned)(ceil_div(total, 256) > 4096 ? 4096 : ceil_div(total, 256))), dim3(256), 0, st, e);
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     return DPOSER_OK;
 }
@@ -1572,7 +1565,7 @@ extern "C" int dposer_lbs_forward_temporal_grad(dposer_body_t h, void* ws, const
     const dim3 grid((unsigned)vchunks, (unsigned)(n_seq * a.nseg));
     if (v_shaped_batched) hipLaunchKernelGGL((k_skin_temporal<NV, true>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((k_skin_temporal<NV, false>), grid, dim3(256), lds, st, a);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 
@@ -1913,14 +1906,14 @@ extern "C" int dposer_pose_pair_errors(const dposer_pose_pair_errors_args* g, vo
         DP_CHECK_ARG((size_t)J * 12 * sizeof(float) <= 64 * 1024, "too many joints");
         hipLaunchKernelGGL(k_pair_err_general, dim3((unsigned)(B * nblk)), dim3(256), J * 12 * sizeof(float), st, a);
     }
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     PairFinalArgs f;
     f.ref = a.ref; f.hyp = a.hyp; f.joints_ref = g->joints_ref; f.joints_hyp = g->joints_hyp; f.ld_j = (int64_t)n_total * 3;
     f.joint_rows = g->joint_rows; f.m = m; f.n_extra = n_extra; f.n_lmk = n_lmk; f.extra_ids = g->extra_vertex_ids; f.lmk_tri = g->lmk_tri;
     f.lmk_bary = g->lmk_bary; f.part = a.part; f.n = n; f.nblk = nblk; f.H = H; f.scale = g->scale; f.min_into = g->min_into ? 1 : 0;
     f.mpvpe = g->mpvpe; f.mpjpe = g->mpjpe; f.mpvpe_h = g->mpvpe_h; f.mpjpe_h = g->mpjpe_h;
     hipLaunchKernelGGL(k_pair_err_final, dim3((unsigned)B), dim3(128), ((size_t)m * 3 + 4) * sizeof(float), st, f);
-    FK_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }
 
@@ -2987,7 +2980,7 @@ extern "C" int dposer_lbs_pack_posedirs_bwd(dposer_body_t h, const float* posedi
         js.job[3] = j; js.job[3].dst_off = n * 8; js.job[3].f32 = 0; js.job[3].split = 1; js.job[3].rows_pad = 256; js.job[3].rows_valid = P < 256 ? P : 256;
         js.job[4] = js.job[3]; js.job[4].dst_off = n * 8 + n256 * 2; js.job[4].split = 2;
     }
-    FK_HIP_LAUNCH(launch_pack(js, posedirs, packed, (hipStream_t)stream));
+    DP_CHECK_HIP(launch_pack(js, posedirs, packed, (hipStream_t)stream));
     return DPOSER_OK;
 }
 static int lbs_bwd_ksplit(int64_t stages) {
@@ -3157,7 +3150,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
         FoldArgs f;
         f.vslot = fold->vertex_slot; f.uniq = fold->slot_vertex; f.ptr = fold->slot_ptr; f.row = fold->entry_row; f.w = fold->entry_weight; f.U = fold->n_slots;
         hipLaunchKernelGGL(k_fold_rows, dim3((unsigned)ceil_div(f.U, 64), (unsigned)batch), dim3(64), 0, st, f, d_verts, d_joints, d_joints_ld, dv_fixed, V, batch);
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
         vg.vslot = fold->vertex_slot; vg.U = fold->n_slots;
     }
     const bool fused = !blend32 && skin_k == 4 && h->jl_ready && h->jl_onepass_ok && batch >= lbs_joint_stream_min() && body_tuning().skin_bwd_fused;
@@ -3196,7 +3189,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
             if (v_shaped_batched) hipLaunchKernelGGL((k_skin_bwd_mfma<4, true>), dim3((unsigned)ceil_div(batch, 4)), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((k_skin_bwd_mfma<4, false>), dim3((unsigned)ceil_div(batch, 4)), dim3(256), 0, st, a);
         }
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     } else {
         SkinBwdArgs a;
         a.vg = vg;
@@ -3205,7 +3198,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
         a.doff_ft = blend32 ? doff : nullptr; a.doff_hi = doff_hi; a.doff_lo = doff_lo;
         a.Cpad = (int)Cpad;
         hipLaunchKernelGGL(k_skin_bwd, dim3((unsigned)ceil_div(V, 256 * 4), (unsigned)batch), dim3(256), (J * 12 + 1536) * sizeof(float), st, a);
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     if (!fused) {
         if (batch >= lbs_joint_stream_min() && h->jl_ready) {
@@ -3220,7 +3213,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
             a.dverts = d_verts; a.vp = vp; a.jptr = joint_ptr; a.jvidx = joint_vidx; a.jw = joint_w; a.dA = dA; a.J = J; a.V = V; a.B = batch;
             hipLaunchKernelGGL(k_skin_bwd_joints_gather, dim3((unsigned)(ceil_div(batch, 8) * 8 * J)), dim3(128), 0, st, a);
         }
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     // d pose_feature [B][486] = d_off [B][3V] @ posedirs^T : split over the vertex dimension.  Only the columns of joints whose pose
     // gradient is wanted are produced (lbs_posed_cols: 189 -> 256 of 512 for the body): compact slabs [Bpad][pe], fewer column tiles
@@ -3239,7 +3232,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
         g.src[0] = posedirs_bwd_packed; g.seg_kblocks[0] = (int)(Cpad / 8); g.nseg = 1; g.ktot_blocks = (int)(Cpad / 8);
         WgradParams wp;
         wp.slab = dpf; wp.slab_stride = Bpad * pe; wp.ld = (int)pe; wp.N_valid = (int)batch; wp.K_valid = (int)((J - 1) * 9 < pe ? (J - 1) * 9 : pe);
-        FK_HIP_LAUNCH(gemm_wgrad(PREC_FP32, SHAPE_MID, g, wp, st));
+        DP_CHECK_HIP(gemm_wgrad(PREC_FP32, SHAPE_MID, g, wp, st));
     } else {
         // d pf = doff_hi pd_hi^T + doff_hi pd_lo^T + doff_lo pd_hi^T: three split-K launches into consecutive slab sets
         const char* pd_hi = (const char*)posedirs_bwd_packed + prow * Cpad * 4;
@@ -3322,13 +3315,13 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
                 DP_CHECK_HIP(hipStreamWaitEvent(st, h->ev_bwd_join[i], 0));
             }
         }
-        FK_HIP_LAUNCH(term_err);
+        DP_CHECK_HIP(term_err);
         ks = 3 * k1;
         if (rowcat) {
             const int64_t n4 = Bpad * pe / 4;
             hipLaunchKernelGGL(k_sum_slabs_rowcat, dim3((unsigned)(n4 < 256 * 2048 ? ceil_div(n4, 256) : 2048)), dim3(256), 0, st, (const float*)dpf, k1, (const float*)slabB, k1,
                                slabB, Bpad, (int)pe);
-            FK_HIP_LAUNCH(hipGetLastError());
+            DP_CHECK_HIP(hipGetLastError());
             dpf = slabB;
             ks = 1;                                                      // (already summed)
         }
@@ -3349,7 +3342,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
         if (ks > 1) {
             const int64_t n4 = Bpad * pe / 4;
             hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)(n4 < 256 * 2048 ? ceil_div(n4, 256) : 2048)), dim3(256), 0, st, dpf, Bpad * pe, ks);
-            FK_HIP_LAUNCH(hipGetLastError());
+            DP_CHECK_HIP(hipGetLastError());
         }
         a.dpf = dpf; a.dpf_slab = Bpad * pe; a.ldpf = pe; a.pf_cols = (int)pe; a.nsplit = 1; a.djrest = d_jrest; a.dG = dG; a.parents = nullptr; a.J = J;
         a.B = batch;
@@ -3364,7 +3357,7 @@ static int lbs_backward_impl(dposer_body_t h, const void* ws_fwd, void* ws_bwd, 
             else if (h->kind == 1) hipLaunchKernelGGL(k_fk_bwd<KinSMPLH>, grid, dim3(64), 0, st, a);
             else hipLaunchKernelGGL(k_fk_bwd<KinSMPLX>, grid, dim3(64), 0, st, a);
         }
-        FK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     return DPOSER_OK;
 }

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "wgrad_batch.h"
 #include "gemm_api.h"
+#include "optim_dev.h"   // AdamScalars
 
 // ---- weight packing -----------------------------------------------------------------------------
 struct PackJob {
@@ -198,7 +199,7 @@ struct CompletionUpdateArgs {   // one optimisation step of DPoserComp.optimize 
     float inv_n;           // 1 / (B * D): both losses are means over the batch (completion.py:147, nn.MSELoss)
     float w_prior, w_data; // loss weights of this step (completion.py:151-155)
     int weighted;
-    float step_size, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps;   // torch.optim.Adam scalars of this step
+    AdamScalars s;         // torch.optim.Adam scalars of this step
     int64_t B;
     int D, Dpad, Cp, num_scales, scale_by_sigma;
     SdeCfg sde;
@@ -352,9 +353,7 @@ struct AdamArgs {          // losses.py:44-58 optimize_fn + torch.optim.Adam + e
     int n_part;
     float grad_scale;      // applied to g before anything else (1/world_size)
     float grad_clip;       // < 0: disabled
-    float step_size;       // lr / (1 - beta1^t)
-    float one_minus_beta1, beta2, one_minus_beta2, eps;
-    float bc2_sqrt;        // sqrt(1 - beta2^t)
+    AdamScalars s;         // step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)
     float ema_one_minus_decay;
     float weight_decay;    // torch.optim.Adam(weight_decay): grad += weight_decay * param (after the clip, before the moments); 0 = off
 };

@@ -15,13 +15,6 @@
 #include "gemm_api.h"
 #include "kernels_api.h"
 
-#define ML_HIP_LAUNCH(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return dposer_set_error(DPOSER_ERR_HIP, std::string(__func__) + ": " + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 namespace {
 constexpr int ML_MAX_LAYERS = 10;      // linear layers: n_blocks + 2
 int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
@@ -120,12 +113,12 @@ extern "C" int dposer_mlp_pack(dposer_mlp_t h, const float* flat, void* packed, 
         PackJobs js;
         js.n = (int)(h->jobs.size() - i0 < (size_t)MAX_PACK_JOBS ? h->jobs.size() - i0 : (size_t)MAX_PACK_JOBS);
         for (int i = 0; i < js.n; ++i) js.job[i] = h->jobs[i0 + i];
-        ML_HIP_LAUNCH(launch_pack(js, flat, packed, (hipStream_t)stream));
+        DP_CHECK_HIP(launch_pack(js, flat, packed, (hipStream_t)stream));
     }
     if (h->Hp != h->H) {
-        ML_HIP_LAUNCH(hipMemsetAsync((char*)packed + h->pk_b[0], 0, (size_t)(h->pk_end - h->pk_b[0]), (hipStream_t)stream));
+        DP_CHECK_HIP(hipMemsetAsync((char*)packed + h->pk_b[0], 0, (size_t)(h->pk_end - h->pk_b[0]), (hipStream_t)stream));
         for (int i = 0; i < h->NL - 1; ++i)
-            ML_HIP_LAUNCH(hipMemcpyAsync((char*)packed + h->pk_b[i], flat + h->b_off[i], (size_t)h->H * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+            DP_CHECK_HIP(hipMemcpyAsync((char*)packed + h->pk_b[i], flat + h->b_off[i], (size_t)h->H * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return DPOSER_OK;
 }
@@ -230,8 +223,8 @@ extern "C" int dposer_mlp_forward(dposer_mlp_t h, const float* flat, const void*
     ml_layout(h, B, (char*)ws_, w);
     const int prec = h->x3 ? PREC_BF16X3 : (h->w32 ? PREC_FP32 : PREC_BF16), KBS = h->KBS, NH = h->NL - 1;
     const bool keep = keep_for_backward != 0;
-    ML_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->Din, h->Kin, h->f32, st));
-    if (h->x3) ML_HIP_LAUNCH(launch_split_ft32(w.xin, w.p_xin.hi, w.p_xin.lo, w.Bpad, h->Kin, st));
+    DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->Din, h->Kin, h->f32, st));
+    if (h->x3) DP_CHECK_HIP(launch_split_ft32(w.xin, w.p_xin.hi, w.p_xin.lo, w.Bpad, h->Kin, st));
     const void* in = w.xin;
     const MlPlanes* in_pl = &w.p_xin;
     for (int i = 0; i < NH; ++i) {
@@ -249,7 +242,7 @@ extern "C" int dposer_mlp_forward(dposer_mlp_t h, const float* flat, const void*
         p.out_lo = h->x3 ? w.p_hb[i].lo : nullptr;
         p.drop = ml_drop(h, train_mode != 0, i, seed, step);
         // (the inference instantiation has no dropout and keeps nothing; train mode or a kept graph take the training one)
-        ML_HIP_LAUNCH(gemm_bias_silu(prec, keep || train_mode != 0, shape, g, p, st));
+        DP_CHECK_HIP(gemm_bias_silu(prec, keep || train_mode != 0, shape, g, p, st));
         in = w.hb[i];
         in_pl = &w.p_hb[i];
     }
@@ -261,7 +254,7 @@ extern "C" int dposer_mlp_forward(dposer_mlp_t h, const float* flat, const void*
                            : ml_gemm(packed + h->pk_w[i], h->Hp / KBS, n_cblk, n_sblk, in, h->Hp / KBS, flops);
         RowMajorParams p;
         p.bias = flat + h->b_off[i]; p.out = out; p.ldc = h->Dout; p.C_valid = h->Dout; p.S_valid = B;
-        ML_HIP_LAUNCH(gemm_rowmajor(prec, shape, g, p, st));
+        DP_CHECK_HIP(gemm_rowmajor(prec, shape, g, p, st));
     }
     return DPOSER_OK;
 }
@@ -308,18 +301,18 @@ extern "C" int dposer_mlp_backward(dposer_mlp_t h, const float* flat, const void
                 t.alg_flops = term == 0 ? flops : 0.0;
                 WgradParams pt = p;
                 pt.slab = p.slab + (int64_t)term * ks * numel;
-                ML_HIP_LAUNCH(gemm_wgrad_tr(shape, t, pt, st));
+                DP_CHECK_HIP(gemm_wgrad_tr(shape, t, pt, st));
             }
         } else if (!h->w32) {
             WgradTrArgs t;
             std::memset(&t, 0, sizeof(t));
             t.dY = dy; t.H = in; t.N = h->nout_pad[i]; t.Kc = h->kin_pad[i]; t.n_cblk = n_cblk; t.n_sblk = n_sblk; t.sblocks = (int)(Bpad / 32); t.ksplit = ks;
             t.alg_flops = flops;
-            ML_HIP_LAUNCH(gemm_wgrad_tr(shape, t, p, st));
+            DP_CHECK_HIP(gemm_wgrad_tr(shape, t, p, st));
         } else {
             GemmArgs g = ml_gemm(dyT, kb_total, n_cblk, n_sblk, inT, kb_total, flops);
             g.ksplit = ks;
-            ML_HIP_LAUNCH(gemm_wgrad(PREC_FP32, shape, g, p, st));
+            DP_CHECK_HIP(gemm_wgrad(PREC_FP32, shape, g, p, st));
         }
         ReduceJob& j = rj.job[rj.n++];
         j.dst_off = h->w_off[i]; j.count = numel; j.src_off = rel(w.slabs + cursor); j.src_stride = numel; j.nsrc = ks * nterm;
@@ -327,14 +320,14 @@ extern "C" int dposer_mlp_backward(dposer_mlp_t h, const float* flat, const void
         return DPOSER_OK;
     };
     // d res (FT, zero on padded rows / columns) and the last layer's parameter gradients
-    ML_HIP_LAUNCH(launch_pack_rows(dout, w.dres, B, Bpad, h->Dout, h->Cp, h->f32, st));
-    if (h->x3) ML_HIP_LAUNCH(launch_split_ft32(w.dres, w.p_dres.hi, w.p_dres.lo, Bpad, h->Cp, st));
+    DP_CHECK_HIP(launch_pack_rows(dout, w.dres, B, Bpad, h->Dout, h->Cp, h->f32, st));
+    if (h->x3) DP_CHECK_HIP(launch_split_ft32(w.dres, w.p_dres.hi, w.p_dres.lo, Bpad, h->Cp, st));
     if (want_w) {
         int nch = 0;
-        ML_HIP_LAUNCH(launch_colsum(h->f32, w.dres, w.cs_last, Bpad, h->Cp, &nch, st, nullptr));
+        DP_CHECK_HIP(launch_colsum(h->f32, w.dres, w.cs_last, Bpad, h->Cp, &nch, st, nullptr));
         if (h->w32) {
-            ML_HIP_LAUNCH(launch_ft_transpose(1, w.dres, w.dresT, Bpad, h->Cp, st));
-            ML_HIP_LAUNCH(launch_ft_transpose(1, w.xin, w.xinT, Bpad, h->Kin, st));
+            DP_CHECK_HIP(launch_ft_transpose(1, w.dres, w.dresT, Bpad, h->Cp, st));
+            DP_CHECK_HIP(launch_ft_transpose(1, w.xin, w.xinT, Bpad, h->Kin, st));
         }
         DP_TRY(wgrad(h->NL - 1, w.dres, w.dresT, w.hb[NH - 1], h->w32 ? w.hT[NH - 1] : nullptr, &w.p_dres, &w.p_hb[NH - 1]));
         add_job(h->b_off[h->NL - 1], h->Dout, w.cs_last, h->Cp, nch);
@@ -353,8 +346,8 @@ extern "C" int dposer_mlp_backward(dposer_mlp_t h, const float* flat, const void
         p.pre = w.pre[i]; p.out = w.dU[i]; p.N = H; p.S_valid = B; p.outT = (want_w && h->w32) ? w.dUT[i] : nullptr; p.Spad = Bpad; p.act = h->d.activation;
         p.part = want_w ? w.part[i] : nullptr;
         p.drop = ml_drop(h, train_mode != 0, i, seed, step);
-        ML_HIP_LAUNCH(gemm_silu_bwd(prec, shape, g, p, st));
-        if (h->x3) ML_HIP_LAUNCH(launch_split_ft32(w.dU[i], w.p_dU[i].hi, w.p_dU[i].lo, Bpad, H, st));      // dU is the next dgrad's and this layer's wgrad operand
+        DP_CHECK_HIP(gemm_silu_bwd(prec, shape, g, p, st));
+        if (h->x3) DP_CHECK_HIP(launch_split_ft32(w.dU[i], w.p_dU[i].hi, w.p_dU[i].lo, Bpad, H, st));      // dU is the next dgrad's and this layer's wgrad operand
         if (want_w) {
             DP_TRY(wgrad(i, w.dU[i], w.dUT[i], i == 0 ? (const void*)w.xin : (const void*)w.hb[i - 1], i == 0 ? (const void*)w.xinT : (const void*)w.hT[i - 1],
                          &w.p_dU[i], i == 0 ? &w.p_xin : &w.p_hb[i - 1]));
@@ -369,8 +362,8 @@ extern "C" int dposer_mlp_backward(dposer_mlp_t h, const float* flat, const void
                            : ml_gemm(packed + h->pk_wT[0], H / KBS, h->Kin / (shape_ct(shape) * 32), (int)(Bpad / (shape_st(shape) * 32)), w.dU[0], H / KBS, xflops);
         RowMajorParams p;
         p.bias = nullptr; p.out = dx; p.ldc = h->Din; p.C_valid = h->Din; p.S_valid = B;
-        ML_HIP_LAUNCH(gemm_rowmajor(prec, shape, g, p, st));
+        DP_CHECK_HIP(gemm_rowmajor(prec, shape, g, p, st));
     }
-    if (want_w && rj.n > 0) ML_HIP_LAUNCH(launch_reduce_grads(rj, w.fbase, flat_grad, st));
+    if (want_w && rj.n > 0) DP_CHECK_HIP(launch_reduce_grads(rj, w.fbase, flat_grad, st));
     return DPOSER_OK;
 }

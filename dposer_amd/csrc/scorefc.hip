@@ -55,13 +55,6 @@ int dposer_set_error(int code, const std::string& msg) {
 extern "C" const char* dposer_last_error(void) { return g_last_error.c_str(); }
 extern "C" int dposer_abi_version(void) { return DPOSER_ABI_VERSION; }
 
-#define DP_HIP_LAUNCH(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return dposer_set_error(DPOSER_ERR_HIP, std::string(__func__) + ": " + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 constexpr int MAX_L = 7;
 
 struct LayerOff {
@@ -325,9 +318,9 @@ extern "C" int dposer_scorefc_pack(dposer_scorefc_t h, const float* flat, void* 
         PackJobs js;
         js.n = (int)(all.size() - i0 < (size_t)MAX_PACK_JOBS ? all.size() - i0 : (size_t)MAX_PACK_JOBS);
         for (int i = 0; i < js.n; ++i) js.job[i] = all[i0 + i];
-        DP_HIP_LAUNCH(launch_pack(js, flat, packed, st));
+        DP_CHECK_HIP(launch_pack(js, flat, packed, st));
     }
-    DP_HIP_LAUNCH(launch_bias_cat(h->bias_jobs, flat, reinterpret_cast<float*>((char*)packed + h->pk_bias_cat), st));
+    DP_CHECK_HIP(launch_bias_cat(h->bias_jobs, flat, reinterpret_cast<float*>((char*)packed + h->pk_bias_cat), st));
     return DPOSER_OK;
 }
 
@@ -608,7 +601,7 @@ static void add_act(const dposer_scorefc_s* h, GemmArgs& g, const void* stored, 
 // (re)build the planes of a stored activation [Bpad][K] (no-op outside bf16x3 mode)
 static int split_act(const dposer_scorefc_s* h, const void* stored, const Planes& pl, int64_t Bpad, int K, hipStream_t st) {
     if (!h->x3) return DPOSER_OK;
-    DP_HIP_LAUNCH(launch_split_ft32(stored, pl.hi, pl.lo, Bpad, K, st));
+    DP_CHECK_HIP(launch_split_ft32(stored, pl.hi, pl.lo, Bpad, K, st));
     return DPOSER_OK;
 }
 
@@ -675,7 +668,7 @@ static int run_gn_layer(dposer_scorefc_s* h, const float* flat, const char* pack
     p.out_hi = h->x3 ? out_pl.hi : nullptr;
     p.out_lo = h->x3 ? out_pl.lo : nullptr;
     if (h->x3 && !((l % 2) == 0 && l + 2 < h->L)) p.out = nullptr;
-    DP_HIP_LAUNCH(gemm_gn(gemm_prec(h), train, shape, g, p, st, h->gs));
+    DP_CHECK_HIP(gemm_gn(gemm_prec(h), train, shape, g, p, st, h->gs));
     return DPOSER_OK;
 }
 
@@ -691,7 +684,7 @@ static int run_post(dposer_scorefc_s* h, const float* flat, const char* packed, 
     p.C_valid = h->D;
     p.S_valid = Bpad;     // padded rows are written too (finite, never read back as samples)
     (void)B;
-    DP_HIP_LAUNCH(gemm_rowmajor(gemm_prec(h), shape, g, p, st));
+    DP_CHECK_HIP(gemm_rowmajor(gemm_prec(h), shape, g, p, st));
     return DPOSER_OK;
 }
 
@@ -715,7 +708,7 @@ static int run_temb(dposer_scorefc_s* h, const float* flat, const char* packed, 
     std::memset(&p.drop, 0, sizeof(p.drop));
     p.out_hi = h->x3 ? w.p_temb.hi : nullptr;      // (bf16x3: temb's operand planes straight from the epilogue)
     p.out_lo = h->x3 ? w.p_temb.lo : nullptr;
-    DP_HIP_LAUNCH(gemm_bias_silu(gemm_prec(h), train, shape, g, p, st));
+    DP_CHECK_HIP(gemm_bias_silu(gemm_prec(h), train, shape, g, p, st));
     return DPOSER_OK;
 }
 
@@ -749,7 +742,7 @@ extern "C" int dposer_scorefc_forward(dposer_scorefc_t h, const float* flat, con
     pa.x = x; pa.labels = labels; pa.freq = freq; pa.xin = w.xin; pa.emb = w.emb;
     pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad; pa.E = h->E;
     pa.fourier = h->d.embedding == DPOSER_EMB_FOURIER; pa.f32 = h->f32;
-    DP_HIP_LAUNCH(launch_prep_infer(pa, st));
+    DP_CHECK_HIP(launch_prep_infer(pa, st));
     DP_TRY(run_temb(h, flat, packed, w, nullptr, nullptr, false, st));
     DP_TRY(split_act(h, w.xin, w.p_xin, w.Bpad, h->Dpad, st));
     const void* in = w.xin;
@@ -765,7 +758,7 @@ extern "C" int dposer_scorefc_forward(dposer_scorefc_t h, const float* flat, con
     OutModelArgs oa;
     oa.res = w.res; oa.labels = labels; oa.sigmas = sigmas; oa.out = out; oa.B = B; oa.D = h->D; oa.Cp = h->Cp;
     oa.num_scales = h->d.num_scales; oa.scale_by_sigma = h->d.scale_by_sigma; oa.fourier = pa.fourier;
-    DP_HIP_LAUNCH(launch_out_model(oa, st));
+    DP_CHECK_HIP(launch_out_model(oa, st));
     return DPOSER_OK;
 }
 
@@ -776,7 +769,7 @@ static int build_time_table(dposer_scorefc_s* h, const float* flat, const char* 
                             int64_t n, const float* freq, hipStream_t st) {
     const int E = h->E, H = h->H, L = h->L;
     const int64_t npad = round_up(n, 32);
-    DP_HIP_LAUNCH(launch_time_embed(labels_dev, label0, n, npad, freq, E, h->d.embedding == DPOSER_EMB_FOURIER, w.tt_emb, st));
+    DP_CHECK_HIP(launch_time_embed(labels_dev, label0, n, npad, freq, E, h->d.embedding == DPOSER_EMB_FOURIER, w.tt_emb, st));
     const int shape = npad % 128 == 0 ? SHAPE_MID : SHAPE_SMALL;
     {
         GemmArgs g = gemm_args(packed + h->pk_wse32, E / 8, E / (shape_ct(shape) * 32), (int)(npad / (shape_st(shape) * 32)));
@@ -785,7 +778,7 @@ static int build_time_table(dposer_scorefc_s* h, const float* flat, const char* 
         p.bias = flat + h->off_se_b; p.out = w.tt_temb; p.pre = nullptr; p.N = E; p.outT = nullptr; p.Spad = npad; p.act = h->d.activation;
         p.out_hi = nullptr; p.out_lo = nullptr;
         std::memset(&p.drop, 0, sizeof(p.drop));
-        DP_HIP_LAUNCH(gemm_bias_silu(PREC_FP32, false, shape, g, p, st));
+        DP_CHECK_HIP(gemm_bias_silu(PREC_FP32, false, shape, g, p, st));
     }
     {
         GemmArgs g = gemm_args(packed + h->pk_wt_all32, E / 8, L * H / (shape_ct(shape) * 32), (int)(npad / (shape_st(shape) * 32)));
@@ -793,7 +786,7 @@ static int build_time_table(dposer_scorefc_s* h, const float* flat, const char* 
         RowMajorParams p;
         p.bias = reinterpret_cast<const float*>(packed + h->pk_bias_cat);
         p.out = w.table; p.ldc = (int64_t)L * H; p.C_valid = L * H; p.S_valid = npad;
-        DP_HIP_LAUNCH(gemm_rowmajor(PREC_FP32, shape, g, p, st));
+        DP_CHECK_HIP(gemm_rowmajor(PREC_FP32, shape, g, p, st));
     }
     return DPOSER_OK;
 }
@@ -858,7 +851,7 @@ static int stage_step_labels(dposer_scorefc_s* h, Ws& w, const dposer_sde_desc* 
     DP_CHECK_HIP(hipMemcpyAsync(w.tt_labels, h->host_stage.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
     if (ve) {
         const SdeDev d = make_sde_dev(to_sde(s));
-        DP_HIP_LAUNCH(launch_ve_labels(w.tt_labels, n, d.smin, d.ratio, st));
+        DP_CHECK_HIP(launch_ve_labels(w.tt_labels, n, d.smin, d.ratio, st));
     }
     return DPOSER_OK;
 }
@@ -883,8 +876,8 @@ static UpdateCommon update_common(dposer_scorefc_s* h, const Ws& w, const dposer
 // sum_b ||grad_b|| and sum_b ||noise_b|| of the call's samples -> norm_sums[0..1]
 static int langevin_norm_sums(const LangevinArgs& a, float* norm_sums, hipStream_t st) {
     int nb = 0;
-    DP_HIP_LAUNCH(launch_langevin_norms(a, &nb, st));
-    DP_HIP_LAUNCH(launch_sum_partials2(a.part, nb, norm_sums, st));
+    DP_CHECK_HIP(launch_langevin_norms(a, &nb, st));
+    DP_CHECK_HIP(launch_sum_partials2(a.part, nb, norm_sums, st));
     return DPOSER_OK;
 }
 
@@ -955,9 +948,9 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
         ea.step = (uint32_t)(start_step - 1);
         ea.z_impA = (noise && observation) ? noise : nullptr;
         if (fused) ea.x_ft = w.xft;
-        DP_HIP_LAUNCH(launch_em_update(ea, st));
+        DP_CHECK_HIP(launch_em_update(ea, st));
     } else {
-        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+        DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
     }
     if (fused) {
         const int shape = final_shape(w.Bpad);
@@ -975,9 +968,9 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
             p.sigmas = sigmas; p.sde = make_sde_dev_at(sc, timesteps_host[gi]); p.t = timesteps_host[gi]; p.num_scales = h->d.num_scales;
             p.scale_by_sigma = sbs_mode(h); p.D = h->D; p.Cp = h->Cp; p.QD = (h->D + 3) >> 2; p.S_valid = B;
             p.seed = seed; p.step = (uint32_t)gi; p.pf = pf;
-            DP_HIP_LAUNCH(gemm_em_step(gemm_prec(h), shape, g, p, st));
+            DP_CHECK_HIP(gemm_em_step(gemm_prec(h), shape, g, p, st));
         }
-        DP_HIP_LAUNCH(launch_ft_to_rows(w.xft, x, w.xmft, x_mean, B, w.Bpad, h->D, h->Dpad, st));
+        DP_CHECK_HIP(launch_ft_to_rows(w.xft, x, w.xmft, x_mean, B, w.Bpad, h->D, h->Dpad, st));
         return DPOSER_OK;
     }
     for (int i = 0; i < n_run; ++i) {
@@ -993,20 +986,20 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
             if (corr == DPOSER_PC_CORR_LANGEVIN) {
                 la.t = t; la.alpha = alpha; la.noise = zc; la.step = cstep;
                 DP_TRY(langevin_norm_sums(la, norm_sums, st));
-                DP_HIP_LAUNCH(launch_langevin_update(la, st));
+                DP_CHECK_HIP(launch_langevin_update(la, st));
             } else {
                 const bool last = k + 1 == nc;
                 aa.t = t; aa.alpha = alpha; aa.noise = zc; aa.step = cstep; aa.imp_step = (uint32_t)gi;
                 aa.obs = last ? observation : nullptr; aa.mask = last ? mask : nullptr;
                 aa.z_imp = (last && nz && observation) ? nz + (int64_t)nc * BD : nullptr;
-                DP_HIP_LAUNCH(launch_ald_update(aa, st));
+                DP_CHECK_HIP(launch_ald_update(aa, st));
             }
         }
         if (corr == DPOSER_PC_CORR_LANGEVIN && observation) {                     // imputation after the corrector + pack
             ea.res = nullptr; ea.t = t; ea.t_next = t; ea.step = (uint32_t)(gi - 1);
             ea.z_pred = ea.z_impB = nullptr; ea.traj = nullptr;
             ea.z_impA = nz ? nz + (int64_t)nc * BD : nullptr;
-            DP_HIP_LAUNCH(launch_em_update(ea, st));
+            DP_CHECK_HIP(launch_em_update(ea, st));
         }
         const bool ahead = corr == DPOSER_PC_CORR_NONE && i + 1 < n_run;          // look-ahead imputation fused into this update
         const float* z_pred = nz ? nz + (int64_t)(nc + (observation ? 1 : 0)) * BD : nullptr;
@@ -1017,12 +1010,12 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
             DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
             ea.res = w.res; ea.t = t; ea.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; ea.step = (uint32_t)gi;
             ea.z_pred = z_pred; ea.z_impB = z_impB; ea.z_impA = z_impA; ea.traj = slot;
-            DP_HIP_LAUNCH(launch_em_update(ea, st));
+            DP_CHECK_HIP(launch_em_update(ea, st));
         } else {
             if (pred != DPOSER_PC_PRED_NONE) DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
             pa.t = t; pa.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; pa.step = (uint32_t)gi; pa.tab = tab;
             pa.z_pred = z_pred; pa.z_impB = z_impB; pa.z_impA = z_impA; pa.traj = slot;
-            DP_HIP_LAUNCH(launch_pc_pred_update(pa, st));
+            DP_CHECK_HIP(launch_pc_pred_update(pa, st));
         }
     }
     return DPOSER_OK;
@@ -1095,11 +1088,11 @@ extern "C" int dposer_langevin_step(dposer_scorefc_t h, const float* flat, const
     a.t = t; a.alpha = alpha; a.snr = snr; a.inv_global_batch = (float)inv_global_batch; a.step = step;
     if (phase == 0) {
         DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
-        DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+        DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
         DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
         DP_TRY(langevin_norm_sums(a, norm_sums, st));
     } else {
-        DP_HIP_LAUNCH(launch_langevin_update(a, st));
+        DP_CHECK_HIP(launch_langevin_update(a, st));
     }
     return DPOSER_OK;
 }
@@ -1124,15 +1117,15 @@ static int prior_loss_impl(dposer_scorefc_t h, const float* flat, const void* pa
     PerturbSharedArgs pa;
     pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
     pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
-    DP_HIP_LAUNCH(launch_perturb_shared(pa, st));
+    DP_CHECK_HIP(launch_perturb_shared(pa, st));
     DP_TRY(run_shared_t(h, flat, packed, w, table_rows > 0 ? row : 0, B, st));
     DenoiseArgs da;
     da.res = w.res; da.x0 = x0; da.xt = w.xt; da.sigmas = sigmas; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = w.loss_part;
     da.t = t; da.inv_n = inv_n; da.weighted = weighted; da.B = B; da.D = h->D; da.Dpad = h->Dpad; da.Cp = h->Cp;
     da.num_scales = h->d.num_scales; da.scale_by_sigma = sbs_mode(h); da.sde = sc;
     int nb = 0;
-    DP_HIP_LAUNCH(launch_denoise(da, &nb, st));
-    DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, loss, st));
+    DP_CHECK_HIP(launch_denoise(da, &nb, st));
+    DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, loss, st));
     return DPOSER_OK;
 }
 extern "C" int dposer_prior_loss(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
@@ -1193,7 +1186,7 @@ extern "C" int dposer_prior_loss_multi(dposer_scorefc_t h, const float* flat, co
     PerturbSharedArgs pa;
     pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t_traj_host[0]; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
     pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
-    DP_HIP_LAUNCH(launch_perturb_shared(pa, st));
+    DP_CHECK_HIP(launch_perturb_shared(pa, st));
     DdimStepArgs da;
     da.res = w.res; da.xt = w.xt; da.xin = w.xin; da.sigmas = sigmas; da.x0 = x0; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = w.loss_part;
     da.t0 = t_traj_host[0]; da.inv_n = inv_n; da.weighted = weighted; da.B = B; da.Bpad = w.Bpad; da.D = h->D; da.Dpad = h->Dpad; da.Cp = h->Cp;
@@ -1202,9 +1195,9 @@ extern "C" int dposer_prior_loss_multi(dposer_scorefc_t h, const float* flat, co
     for (int i = 0; i < n_steps; ++i) {
         DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
         da.t = t_traj_host[i]; da.t_next = t_traj_host[i + 1]; da.last = i + 1 == n_steps;
-        DP_HIP_LAUNCH(launch_ddim_step(da, &nb, st));
+        DP_CHECK_HIP(launch_ddim_step(da, &nb, st));
     }
-    DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, loss, st));
+    DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, loss, st));
     return DPOSER_OK;
 }
 
@@ -1228,15 +1221,15 @@ extern "C" int dposer_prior_red_diff(dposer_scorefc_t h, const float* flat, cons
     PerturbSharedArgs pa;
     pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
     pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
-    DP_HIP_LAUNCH(launch_perturb_shared(pa, st));
+    DP_CHECK_HIP(launch_perturb_shared(pa, st));
     DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
     RedDiffArgs ra;
     ra.res = w.res; ra.x0 = x0; ra.z_in = z; ra.sigmas = sigmas; ra.eps_pred = eps_pred; ra.grad = grad; ra.loss_part = w.loss_part;
     ra.t = t; ra.inv_batch = inv_batch; ra.B = B; ra.D = h->D; ra.Cp = h->Cp; ra.num_scales = h->d.num_scales; ra.scale_by_sigma = sbs_mode(h);
     ra.sde = sc; ra.seed = seed; ra.step = step;
     int nb = 0;
-    DP_HIP_LAUNCH(launch_red_diff(ra, &nb, st));
-    DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, loss, st));
+    DP_CHECK_HIP(launch_red_diff(ra, &nb, st));
+    DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, loss, st));
     return DPOSER_OK;
 }
 
@@ -1269,18 +1262,15 @@ extern "C" int dposer_completion_optimize(dposer_scorefc_t h, const float* flat,
         PerturbSharedArgs pa;
         pa.x0 = x; pa.z_in = noise ? noise + (int64_t)i * BD : nullptr; pa.xin = w.xin; pa.xt = w.xt; pa.t = t_host[i]; pa.B = B; pa.Bpad = w.Bpad;
         pa.D = h->D; pa.Dpad = h->Dpad; pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step0 + (uint32_t)i;
-        DP_HIP_LAUNCH(launch_perturb_shared(pa, st));
+        DP_CHECK_HIP(launch_perturb_shared(pa, st));
         DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
         CompletionUpdateArgs ua;
         ua.res = w.res; ua.xt = w.xt; ua.obs = observation; ua.mask = mask; ua.sigmas = sigmas; ua.x = x; ua.m = adam_m; ua.v = adam_v;
         ua.t = t_host[i]; ua.inv_n = (float)(1.0 / ((double)B * (double)h->D)); ua.w_prior = w_prior_host[i]; ua.w_data = w_data_host[i];
         ua.weighted = weighted_host[i];
-        const double k = (double)(i + 1);
-        ua.step_size = (float)(lr / (1.0 - std::pow(beta1, k)));                   // torch: step_size = lr / bias_correction1
-        ua.one_minus_beta1 = (float)(1.0 - beta1); ua.beta2 = (float)beta2; ua.one_minus_beta2 = (float)(1.0 - beta2);
-        ua.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, k)); ua.eps = (float)eps;
+        ua.s = adam_scalars(lr, beta1, beta2, eps, i + 1);
         ua.B = B; ua.D = h->D; ua.Dpad = h->Dpad; ua.Cp = h->Cp; ua.num_scales = h->d.num_scales; ua.scale_by_sigma = sbs_mode(h); ua.sde = sc;
-        DP_HIP_LAUNCH(launch_completion_update(ua, st));
+        DP_CHECK_HIP(launch_completion_update(ua, st));
     }
     return DPOSER_OK;
 }
@@ -1320,7 +1310,7 @@ static int run_wgrad(dposer_scorefc_s* h, const void* dyT, int n_rows_pad, int n
             t.alg_flops = term == 0 ? g.alg_flops : 0.0;
             WgradParams pt = p;
             pt.slab = p.slab + (int64_t)term * ks * numel;
-            DP_HIP_LAUNCH(gemm_wgrad_tr(shape, t, pt, st));
+            DP_CHECK_HIP(gemm_wgrad_tr(shape, t, pt, st));
         }
         ReduceJob& j = rj.job[rj.n++];
         j.dst_off = flat_off; j.count = numel; j.src_off = slab_cursor; j.src_stride = numel; j.nsrc = 3 * ks;
@@ -1332,9 +1322,9 @@ static int run_wgrad(dposer_scorefc_s* h, const void* dyT, int n_rows_pad, int n
         std::memset(&t, 0, sizeof(t));
         t.dY = dy; t.H = in; t.N = n_rows_pad; t.Kc = k_rows_pad; t.n_cblk = n_cblk; t.n_sblk = n_sblk; t.sblocks = (int)(Bpad / 32); t.ksplit = ks;
         t.alg_flops = g.alg_flops;
-        DP_HIP_LAUNCH(gemm_wgrad_tr(shape, t, p, st));
+        DP_CHECK_HIP(gemm_wgrad_tr(shape, t, p, st));
     } else {
-        DP_HIP_LAUNCH(gemm_wgrad(h->w32 ? PREC_FP32 : PREC_BF16, shape, g, p, st));
+        DP_CHECK_HIP(gemm_wgrad(h->w32 ? PREC_FP32 : PREC_BF16, shape, g, p, st));
     }
     ReduceJob& j = rj.job[rj.n++];
     j.dst_off = flat_off; j.count = numel; j.src_off = slab_cursor; j.src_stride = numel; j.nsrc = ks;
@@ -1369,7 +1359,7 @@ static int forward_core_train(dposer_scorefc_s* h, const float* flat, const char
         p.out_hi = h->x3 ? w.p_h[l].hi : nullptr;             // bf16x3: operand planes from the epilogue; fp32 tiles only where they are a residual input
         p.out_lo = h->x3 ? w.p_h[l].lo : nullptr;
         if (h->x3 && !((l % 2) == 0 && l + 2 < L)) p.out = nullptr;
-        DP_HIP_LAUNCH(gemm_gn(gemm_prec(h), true, shape, g, p, st, h->gs));
+        DP_CHECK_HIP(gemm_gn(gemm_prec(h), true, shape, g, p, st, h->gs));
     }
     return run_post(h, flat, packed, w.hbuf[L - 1], w.p_h[L - 1], w.res, B, w.Bpad, st);
 }
@@ -1647,22 +1637,22 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         }
         // operands that only depend on the forward pass
         if (!tr) {
-            DP_HIP_LAUNCH(launch_ft_transpose(h->f32, w.xin, w.xinT, Bpad, h->Dpad, sw));
-            DP_HIP_LAUNCH(launch_ft_transpose(h->f32, w.emb, w.embT, Bpad, E, sw));
+            DP_CHECK_HIP(launch_ft_transpose(h->f32, w.xin, w.xinT, Bpad, h->Dpad, sw));
+            DP_CHECK_HIP(launch_ft_transpose(h->f32, w.emb, w.embT, Bpad, E, sw));
         }
         // post_dense: bias (column sums of dres: left by k_dsm in the fused step, else a k_colsum launch here) and weight
         if (dsm_cs_rows > 0) n_chunks_post = dsm_cs_rows;
-        else DP_HIP_LAUNCH(launch_colsum(h->f32, w.dres, w.cs_part_post, Bpad, h->Cp, &n_chunks_post, sw, nullptr));
+        else DP_CHECK_HIP(launch_colsum(h->f32, w.dres, w.cs_part_post, Bpad, h->Cp, &n_chunks_post, sw, nullptr));
         if (h->x3) {
             DP_TRY(run_wgrad(h, nullptr, h->Cp, h->D, nullptr, H, H, Bpad, w.slabs, slab_cursor, (int64_t)h->D * H, h->off_post_w, rj, sw, nullptr, nullptr, &w.p_dres, &w.p_h[L - 1]));
         } else if (tr) {
             DP_TRY(run_wgrad(h, nullptr, h->Cp, h->D, nullptr, H, H, Bpad, w.slabs, slab_cursor, (int64_t)h->D * H, h->off_post_w, rj, sw, w.dres, w.hbuf[L - 1]));
         } else {
-            DP_HIP_LAUNCH(launch_ft_transpose(h->f32, w.dres, w.dresT, Bpad, h->Cp, sw));
+            DP_CHECK_HIP(launch_ft_transpose(h->f32, w.dres, w.dresT, Bpad, h->Cp, sw));
             DP_TRY(run_wgrad(h, w.dresT, h->Cp, h->D, w.hT[L - 1], H, H, Bpad, w.slabs, slab_cursor, (int64_t)h->D * H, h->off_post_w, rj, sw));
         }
     } else if (loss_sum && loss_sum->n > 0) {
-        DP_HIP_LAUNCH(launch_sum_partials(loss_sum->part, loss_sum->n, loss_sum->out, st));
+        DP_CHECK_HIP(launch_sum_partials(loss_sum->part, loss_sum->n, loss_sum->out, st));
     }
     const int gshape = gnbwd_shape(Bpad, h->gs, !h->f32);
     const int ws_rows = (int)(Bpad / (shape_st(gshape) * 32)) * shape_ws(gshape);   // partial rows written by the dgrad epilogue
@@ -1699,7 +1689,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         p.dy_hi = h->x3 ? w.p_dy[j].hi : nullptr;            // bf16x3: dy is only ever a GEMM operand -- its planes, no fp32 tiles
         p.dy_lo = h->x3 ? w.p_dy[j].lo : nullptr;
         if (h->x3) p.dy = nullptr;
-        DP_HIP_LAUNCH(gemm_gn_bwd(prec, gshape, g, p, st, h->gs));
+        DP_CHECK_HIP(gemm_gn_bwd(prec, gshape, g, p, st, h->gs));
         if (!want_w) continue;
         if (two) {
             DP_CHECK_HIP(hipEventRecord(h->ev_layer[j], st));
@@ -1719,9 +1709,9 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
             double fl = 0.0;
             for (int l = grp_lo[cur_group]; l <= grp_hi[cur_group]; ++l) fl += 2.0 * (double)B * H * ((l >= 1 ? (double)H : 0.0) + (double)E);
             wb.alg_flops = fl;
-            DP_HIP_LAUNCH(gemm_wgrad_tr_batch(wb, sw));
+            DP_CHECK_HIP(gemm_wgrad_tr_batch(wb, sw));
             for (int l = grp_hi[cur_group]; l >= grp_lo[cur_group]; --l) add_layer_jobs(l);
-            DP_HIP_LAUNCH(launch_reduce_all(wb, rj, w.slabs, flat_grad, sw));          // partial tiles + the group's small reductions: one launch
+            DP_CHECK_HIP(launch_reduce_all(wb, rj, w.slabs, flat_grad, sw));          // partial tiles + the group's small reductions: one launch
             rj.n = 0;
             DP_TRY(mark_final(h, sink, L - 1 - grp_hi[cur_group], grp_hi[cur_group] - grp_lo[cur_group] + 1, sw));
             if (j == 0) front_a_done = true;
@@ -1740,7 +1730,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
             add_layer_jobs(j);
             // layer j's gradient (and everything behind it in the flat buffer) is final: the data-parallel all-reduce of this
             // bucket can start while the remaining layers are still being differentiated
-            if (rj.n > 0) DP_HIP_LAUNCH(launch_reduce_grads(rj, w.slabs, flat_grad, sw));
+            if (rj.n > 0) DP_CHECK_HIP(launch_reduce_grads(rj, w.slabs, flat_grad, sw));
             rj.n = 0;
             DP_TRY(mark_final(h, sink, L - 1 - j, 1, sw));
             if (j == 0) front_a_done = true;
@@ -1753,7 +1743,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         add_act(h, g, w.dy[0], w.p_dy[0], H / KBS);
         RowMajorParams p;
         p.bias = nullptr; p.out = dx; p.ldc = h->D; p.C_valid = h->D; p.S_valid = B;
-        DP_HIP_LAUNCH(gemm_rowmajor(prec, shape, g, p, st));
+        DP_CHECK_HIP(gemm_rowmajor(prec, shape, g, p, st));
     }
     if (!want_w) return DPOSER_OK;
     // time branch: dtemb = sum_l dy_l @ Wt_l ; dU = dtemb * silu'(u)
@@ -1770,13 +1760,13 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
                 add_act(h, gl, w.dy[l], w.p_dy[l], H / KBS);
                 PartialFTParams pp;
                 pp.out = w.dU_part + (int64_t)l * Bpad * E; pp.N = E; pp.split_stride = 0;
-                DP_HIP_LAUNCH(gemm_partial_ft(prec, shape, gl, pp, st));
+                DP_CHECK_HIP(gemm_partial_ft(prec, shape, gl, pp, st));
             }
             SiLUBwdReduceArgs ra;
             ra.part = w.dU_part; ra.nsplit = L; ra.split_stride = Bpad * (int64_t)E; ra.pre = w.upre; ra.out = w.dU; ra.cs_part = w.silu_part;
             ra.N = E; ra.act = h->d.activation; ra.f32 = h->f32; ra.B = B; ra.Spad = Bpad;
             int nb = 0;
-            DP_HIP_LAUNCH(launch_silu_bwd_reduce_ft(ra, w.p_dU.hi, w.p_dU.lo, (int)silu_part_rows(Bpad, true), &nb, st));      // (writes dU's operand planes too)
+            DP_CHECK_HIP(launch_silu_bwd_reduce_ft(ra, w.p_dU.hi, w.p_dU.lo, (int)silu_part_rows(Bpad, true), &nb, st));      // (writes dU's operand planes too)
             silu_rows = nb;
         } else {
         g_next_flops = 2.0 * (double)B * E * L * H;
@@ -1790,12 +1780,12 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
             g.split_segments = 1;
             PartialFTParams pp;
             pp.out = w.dU_part; pp.N = E; pp.split_stride = Bpad * (int64_t)E;
-            DP_HIP_LAUNCH(gemm_partial_ft(prec, shape, g, pp, st));
+            DP_CHECK_HIP(gemm_partial_ft(prec, shape, g, pp, st));
             SiLUBwdReduceArgs ra;
             ra.part = w.dU_part; ra.nsplit = L; ra.split_stride = Bpad * (int64_t)E; ra.pre = w.upre; ra.out = w.dU; ra.cs_part = w.silu_part;
             ra.N = E; ra.act = h->d.activation; ra.f32 = h->f32; ra.B = B; ra.Spad = Bpad;
             int nb = 0;
-            DP_HIP_LAUNCH(launch_silu_bwd_reduce(ra, (int)silu_part_rows(Bpad), &nb, st));
+            DP_CHECK_HIP(launch_silu_bwd_reduce(ra, (int)silu_part_rows(Bpad), &nb, st));
             silu_rows = nb;
         } else {
         SiLUBwdParams p;
@@ -1803,7 +1793,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         p.part = w.silu_part;                                            // the shared embedding's bias gradient: no column-sum launch over dU
         std::memset(&p.drop, 0, sizeof(p.drop));
         silu_rows = (int)(Bpad / (shape_st(shape) * 32)) * shape_ws(shape);
-        DP_HIP_LAUNCH(gemm_silu_bwd(prec, shape, g, p, st));
+        DP_CHECK_HIP(gemm_silu_bwd(prec, shape, g, p, st));
         }
         }
     }
@@ -1820,13 +1810,13 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
     if (batched) {
         if (slab_cursor > w.slab_elems - lane_room) return dposer_set_error(DPOSER_ERR_BAD_ARG, "backward: slab buffer too small for the batched wgrad launch");
         wb.alg_flops = 2.0 * (double)B * H * ((double)(L - 1) * H + (double)L * E) + (se_in_batch ? 2.0 * (double)B * E * E : 0.0);
-        DP_HIP_LAUNCH(gemm_wgrad_tr_batch(wb, st));
+        DP_CHECK_HIP(gemm_wgrad_tr_batch(wb, st));
         if (h->x3) {     // the other two product terms: the same plan on the other planes, each into its own partial set
             for (int term = 1; term < 3; ++term) {
                 WgradBatchArgs wt;
                 if (!plan_wgrad_lanes(h, w, 0, L - 1, se_in_batch, wt, term) || wt.nprob != wb.nprob) return dposer_set_error(DPOSER_ERR_BAD_ARG, "backward: lane plan changed between the product terms");
                 wt.alg_flops = 0.0;
-                DP_HIP_LAUNCH(gemm_wgrad_tr_batch(wt, st));
+                DP_CHECK_HIP(gemm_wgrad_tr_batch(wt, st));
             }
         }
     }
@@ -1842,8 +1832,8 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         ReduceJob& jb = rj.job[rj.n++];
         jb.dst_off = h->nograd_lo[i]; jb.count = h->nograd_hi[i] - h->nograd_lo[i]; jb.src_off = 0; jb.src_stride = 0; jb.nsrc = 0;
     }
-    if (batched) DP_HIP_LAUNCH(launch_reduce_all(wb, rj, w.slabs, flat_grad, st));      // (batched: sw == st) partial tiles + every small reduction of the step
-    else if (rj.n > 0) DP_HIP_LAUNCH(launch_reduce_grads(rj, w.slabs, flat_grad, sw));
+    if (batched) DP_CHECK_HIP(launch_reduce_all(wb, rj, w.slabs, flat_grad, st));      // (batched: sw == st) partial tiles + every small reduction of the step
+    else if (rj.n > 0) DP_CHECK_HIP(launch_reduce_grads(rj, w.slabs, flat_grad, sw));
     rj.n = 0;
     if (batched && has_events) {     // nothing was final before this point: every bucket becomes final with the last reduction
         DP_TRY(mark_final(h, sink, 0, L + 1, sw));
@@ -1878,7 +1868,7 @@ static int dsm_loss_fwd_bwd_impl(dposer_scorefc_t h, const float* flat, const vo
     pa.x0 = batch_x; pa.t_in = t_in; pa.z_in = z_in; pa.freq = freq; pa.xin = w.xin; pa.emb = w.emb; pa.t_out = w.tbuf; pa.z_out = w.zbuf;
     pa.B = B; pa.Bpad = Bpad; pa.D = h->D; pa.Dpad = h->Dpad; pa.E = h->E; pa.fourier = h->d.embedding == DPOSER_EMB_FOURIER; pa.f32 = h->f32; pa.sde = sc; pa.eps = eps;
     pa.seed = seed; pa.step = step;
-    DP_HIP_LAUNCH(launch_prep_train(pa, st));
+    DP_CHECK_HIP(launch_prep_train(pa, st));
     DP_TRY(forward_core_train(h, flat, packed, w, B, true, seed, step, st));
     int nb = 0;
     DsmArgs da;
@@ -1886,7 +1876,7 @@ static int dsm_loss_fwd_bwd_impl(dposer_scorefc_t h, const float* flat, const vo
     da.cs_part = w.cs_part_post;
     da.D = h->D; da.Dpad = h->Dpad; da.Cp = h->Cp; da.num_scales = h->d.num_scales; da.scale_by_sigma = h->d.scale_by_sigma;
     da.f32 = h->f32; da.fourier = h->d.embedding == DPOSER_EMB_FOURIER; da.grad_scale = (float)(1.0 / ((double)B * (double)h->D)); da.sde = sc;
-    DP_HIP_LAUNCH(launch_dsm(da, &nb, st));
+    DP_CHECK_HIP(launch_dsm(da, &nb, st));
     const SumJob loss_sum{w.loss_part, nb, loss};                      // summed by one block of the LAST reduction launch of the backward
     return backward_core(h, flat, packed, w, B, true, seed, step, flat_grad, nullptr, sink, st, &loss_sum, nb);
 }
@@ -1942,12 +1932,12 @@ extern "C" int dposer_scorefc_forward_train(dposer_scorefc_t h, const float* fla
     pa.x = x; pa.labels = labels; pa.freq = freq; pa.xin = w.xin; pa.emb = w.emb;
     pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad; pa.E = h->E;
     pa.fourier = h->d.embedding == DPOSER_EMB_FOURIER; pa.f32 = h->f32;
-    DP_HIP_LAUNCH(launch_prep_infer(pa, st));
+    DP_CHECK_HIP(launch_prep_infer(pa, st));
     DP_TRY(forward_core_train(h, flat, packed, w, B, train_mode != 0, seed, step, st));
     OutModelArgs oa;
     oa.res = w.res; oa.labels = labels; oa.sigmas = sigmas; oa.out = out; oa.B = B; oa.D = h->D; oa.Cp = h->Cp;
     oa.num_scales = h->d.num_scales; oa.scale_by_sigma = h->d.scale_by_sigma; oa.fourier = pa.fourier;
-    DP_HIP_LAUNCH(launch_out_model(oa, st));
+    DP_CHECK_HIP(launch_out_model(oa, st));
     return DPOSER_OK;
 }
 
@@ -1968,7 +1958,7 @@ extern "C" int dposer_scorefc_backward(dposer_scorefc_t h, const float* flat, co
     da.dout = dout; da.labels = labels; da.sigmas = sigmas; da.dres = w.dres; da.B = B; da.Bpad = w.Bpad; da.D = h->D; da.Cp = h->Cp;
     da.num_scales = h->d.num_scales; da.scale_by_sigma = h->d.scale_by_sigma; da.fourier = h->d.embedding == DPOSER_EMB_FOURIER;
     da.f32 = h->f32;
-    DP_HIP_LAUNCH(launch_dres_from_dout(da, st));
+    DP_CHECK_HIP(launch_dres_from_dout(da, st));
     return backward_core(h, flat, packed, w, B, train_mode != 0, seed, step, flat_grad, dx, nullptr, st);
 }
 
@@ -1999,7 +1989,7 @@ static int forward_core_guided(dposer_scorefc_s* h, const float* flat, const cha
         p.out_hi = h->x3 ? w.p_h[l].hi : nullptr;
         p.out_lo = h->x3 ? w.p_h[l].lo : nullptr;
         if (h->x3 && !((l % 2) == 0 && l + 2 < L)) p.out = nullptr;
-        DP_HIP_LAUNCH(gemm_gn(gemm_prec(h), true, shape, g, p, st, h->gs));
+        DP_CHECK_HIP(gemm_gn(gemm_prec(h), true, shape, g, p, st, h->gs));
     }
     return run_post(h, flat, packed, w.hbuf[L - 1], w.p_h[L - 1], w.res, B, w.Bpad, st);
 }
@@ -2036,7 +2026,7 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
     static_cast<UpdateCommon&>(ga) = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
     ga.obs = observation; ga.mask = mask; ga.dres = w.dres; ga.part = w.loss_part; ga.norm_sq = w.scalar; ga.dx = w.zbuf;
     ga.nonfinite = nonfinite_step; ga.grad_step = grad_step; ga.project = project;
-    DP_HIP_LAUNCH(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+    DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
     for (int i = 0; i < n_run; ++i) {
         const int gi = start_step + i;
         const float* nz = noise ? noise + (int64_t)i * k_noise * BD : nullptr;
@@ -2045,10 +2035,10 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
         ga.traj = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
         DP_TRY(forward_core_guided(h, flat, packed, w, i, B, st));
         int nb = 0;
-        DP_HIP_LAUNCH(launch_guided_resid(ga, &nb, st));
-        DP_HIP_LAUNCH(launch_sum_partials(w.loss_part, nb, w.scalar, st));
+        DP_CHECK_HIP(launch_guided_resid(ga, &nb, st));
+        DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, w.scalar, st));
         DP_TRY(backward_core(h, flat, packed, w, B, false, 0, 0, nullptr, w.zbuf, nullptr, st));
-        DP_HIP_LAUNCH(launch_guided_update(ga, st));
+        DP_CHECK_HIP(launch_guided_update(ga, st));
     }
     return DPOSER_OK;
 }
@@ -2058,9 +2048,21 @@ extern "C" int dposer_grad_sqnorm(const float* grad, int64_t n, float* scratch, 
     DP_CHECK_ARG(grad && scratch && n >= 0, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     int nb = 0;
-    DP_HIP_LAUNCH(launch_sqnorm(grad, n, scratch + 16, &nb, st));
-    DP_HIP_LAUNCH(launch_sum_partials(scratch + 16, nb, scratch, st));
+    DP_CHECK_HIP(launch_sqnorm(grad, n, scratch + 16, &nb, st));
+    DP_CHECK_HIP(launch_sum_partials(scratch + 16, nb, scratch, st));
     return DPOSER_OK;
+}
+// the optimizer kernels' argument block (every field): nb = number of k_sqnorm partials in scratch + 16, 0 = the sum is in scratch[0] already
+static void fill_adam_args(AdamArgs& a, float* flat, const float* grad, float* m, float* v, float* ema, int64_t n, const int64_t* skip_lo_host,
+                           const int64_t* skip_hi_host, int32_t n_skip, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           double grad_clip, double grad_scale, int64_t adam_step, double ema_one_minus_decay, float* scratch, int nb) {
+    a.sq_part = scratch + 16; a.n_part = nb;
+    a.p = flat; a.g = grad; a.m = m; a.v = v; a.ema = ema; a.n = n;
+    for (int i = 0; i < 2; ++i) { a.skip_lo[i] = i < n_skip ? skip_lo_host[i] : 0; a.skip_hi[i] = i < n_skip ? skip_hi_host[i] : 0; }
+    a.sqnorm = scratch; a.grad_scale = (float)grad_scale; a.grad_clip = (float)grad_clip;
+    a.s = adam_scalars(lr, beta1, beta2, eps, (double)adam_step);
+    a.ema_one_minus_decay = (float)ema_one_minus_decay;
+    a.weight_decay = (float)weight_decay;
 }
 static int adam_step_impl(float* flat, const float* grad, float* m, float* v, float* ema, int64_t n, const int64_t* skip_lo_host,
                           const int64_t* skip_hi_host, int32_t n_skip, double lr, double beta1, double beta2, double eps, double grad_clip,
@@ -2099,19 +2101,11 @@ static int adam_step_impl(float* flat, const float* grad, float* m, float* v, fl
     DP_CHECK_ARG(n_skip >= 0 && n_skip <= 2, "at most two no-gradient ranges");
     hipStream_t st = (hipStream_t)stream;
     int nb = 0;
-    if (!presummed) DP_HIP_LAUNCH(launch_sqnorm(grad, n, scratch + 16, &nb, st));     // (the partials are added up by k_adam_ema)
+    if (!presummed) DP_CHECK_HIP(launch_sqnorm(grad, n, scratch + 16, &nb, st));     // (the partials are added up by k_adam_ema)
     AdamArgs a;
-    a.sq_part = scratch + 16; a.n_part = nb;
-    a.p = flat; a.g = grad; a.m = m; a.v = v; a.ema = ema; a.n = n;
-    for (int i = 0; i < 2; ++i) { a.skip_lo[i] = i < n_skip ? skip_lo_host[i] : 0; a.skip_hi[i] = i < n_skip ? skip_hi_host[i] : 0; }
-    a.sqnorm = scratch; a.grad_scale = (float)grad_scale; a.grad_clip = (float)grad_clip;
-    const double bc1 = 1.0 - std::pow(beta1, (double)adam_step);
-    a.step_size = (float)(lr / bc1);                                   // torch: step_size = lr / bias_correction1
-    a.one_minus_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)adam_step));
-    a.ema_one_minus_decay = (float)ema_one_minus_decay;
-    a.weight_decay = (float)weight_decay;
-    DP_HIP_LAUNCH(launch_adam_ema(a, st));
+    fill_adam_args(a, flat, grad, m, v, ema, n, skip_lo_host, skip_hi_host, n_skip, lr, beta1, beta2, eps, weight_decay, grad_clip, grad_scale,
+                   adam_step, ema_one_minus_decay, scratch, nb);
+    DP_CHECK_HIP(launch_adam_ema(a, st));
     return DPOSER_OK;
 }
 
@@ -2135,22 +2129,13 @@ extern "C" int dposer_scorefc_adam_pack_step(dposer_scorefc_t h, float* flat, co
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = h->nparams;
     int nb = 0;
-    if (!presummed) DP_HIP_LAUNCH(launch_sqnorm(grad, n, scratch + 16, &nb, st));
+    if (!presummed) DP_CHECK_HIP(launch_sqnorm(grad, n, scratch + 16, &nb, st));
     AdamPackArgs ap = h->adam_pack;
-    AdamArgs& a = ap.a;
-    a.sq_part = scratch + 16; a.n_part = nb;
-    a.p = flat; a.g = grad; a.m = m; a.v = v; a.ema = ema; a.n = n;
-    for (int i = 0; i < 2; ++i) { a.skip_lo[i] = i < n_skip ? skip_lo_host[i] : 0; a.skip_hi[i] = i < n_skip ? skip_hi_host[i] : 0; }
-    a.sqnorm = scratch; a.grad_scale = (float)grad_scale; a.grad_clip = (float)grad_clip;
-    const double bc1 = 1.0 - std::pow(beta1, (double)adam_step);
-    a.step_size = (float)(lr / bc1);
-    a.one_minus_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)adam_step));
-    a.ema_one_minus_decay = (float)ema_one_minus_decay;
-    a.weight_decay = (float)weight_decay;
+    fill_adam_args(ap.a, flat, grad, m, v, ema, h->nparams, skip_lo_host, skip_hi_host, n_skip, lr, beta1, beta2, eps, weight_decay, grad_clip,
+                   grad_scale, adam_step, ema_one_minus_decay, scratch, nb);
     ap.packed = (unsigned char*)packed;
     ap.write_through = score_tuning().adam_write_through;
-    DP_HIP_LAUNCH(launch_adam_pack(ap, st));
+    DP_CHECK_HIP(launch_adam_pack(ap, st));
     return DPOSER_OK;
 }
 

@@ -16,15 +16,8 @@
 #include <string>
 
 #include "common.h"
+#include "optim_dev.h"
 #include "rng.h"
-#include "rot_dev.h"
-
-#define SP_HIP_LAUNCH(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return dposer_set_error(DPOSER_ERR_HIP, std::string(__func__) + ": " + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 namespace {
 
@@ -41,27 +34,7 @@ __device__ __forceinline__ float wave_min(float v) {
     return v;
 }
 
-// offline_normalize(from_axis=True) (lib/dataset/AMASS.py:126-137), the expression of tasks.hip md_norm: mode 0 identity, 1 z-score
-// (a = mean, b = std), 2 min-max (a = min, b = max)
-__device__ __forceinline__ float sp_norm(float p, int mode, const float* a, const float* b, int c) {
-    if (mode == 1) return (p - a[c]) / b[c];
-    if (mode == 2) return 2.0f * (p - a[c]) / (b[c] - a[c]) - 1.0f;
-    return p;
-}
-// normalised network input of one body joint: 3 axis-angle coordinates, or (rot6d) the first two columns of its rotation matrix, row-major
-// (R00 R01 R10 R11 R20 R21: lib/utils/transforms.py:238-255) -- tasks.hip k_md_normalize / k_md_normalize6d
-__device__ __forceinline__ void sp_norm_joint(const float* q, int j, int mode, const float* a, const float* b, bool rot6d, float* xn_row) {
-    if (rot6d) {
-        const Mat3 R = rodrigues(q[0], q[1], q[2]);
-        const float six[6] = {R.m[0], R.m[1], R.m[3], R.m[4], R.m[6], R.m[7]};
-#pragma unroll
-        for (int e = 0; e < 6; ++e) xn_row[j * 6 + e] = sp_norm(six[e], mode, a, b, j * 6 + e);
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) xn_row[j * 3 + c] = sp_norm(q[c], mode, a, b, j * 3 + c);
-    }
-}
-
+// normalised network input of every body joint (optim_dev.h pose_norm_joint); one thread per (image, joint)
 __global__ void __launch_bounds__(256) k_sp_normalize(const float* body_pose, int NBJ, int mode, const float* a, const float* b, int rot6d,
                                                       float* xn, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -69,7 +42,7 @@ __global__ void __launch_bounds__(256) k_sp_normalize(const float* body_pose, in
     const int64_t img = i / NBJ;
     const int j = (int)(i % NBJ);
     const int Dn = NBJ * (rot6d ? 6 : 3);
-    sp_norm_joint(body_pose + img * NBJ * 3 + j * 3, j, mode, a, b, rot6d != 0, xn + img * Dn);
+    pose_norm_joint(body_pose + img * NBJ * 3 + j * 3, j, mode, a, b, rot6d != 0, xn + img * Dn, j);
 }
 
 // the prior's z when none is injected: Philox keyed by the GLOBAL image index (row0 + b), so a batch split into groups draws the same
@@ -239,15 +212,12 @@ template <bool FINAL> __global__ void __launch_bounds__(64) k_sp_body_grad(FitAr
     }
 }
 
-// torch.optim.Adam, single-tensor arithmetic (tasks.hip k_md_update)
-struct AdamScalars { float step_size, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps; };
+// torch.optim.Adam (optim_dev.h adam_step) on a parameter with its moments in memory
 __device__ __forceinline__ float sp_adam(float p, float g, float* m_, float* v_, const AdamScalars& s) {
     float m = *m_, v = *v_;
-    m = m + (g - m) * s.one_minus_beta1;
-    v = v * s.beta2 + s.one_minus_beta2 * (g * g);
-    const float denom = sqrtf(v) / s.bc2_sqrt + s.eps;
+    p = adam_step(p, g, m, v, s);
     *m_ = m; *v_ = v;
-    return p - s.step_size * (m / denom);
+    return p;
 }
 
 // camera stage update: Adam over [global_orient | cam_t] (smplify.py:207-208); one thread per image
@@ -300,31 +270,9 @@ __global__ void __launch_bounds__(256) k_sp_body_update(BodyUpdate u) {
     }
     const int j = sl - 1;
     float* q = u.body_pose + b * 3 * u.NBJ + j * 3;
+    const int Dn = (u.rot6d ? 6 : 3) * u.NBJ;
     float gq[3];
-    if (u.rot6d) {
-        const int Dn = 6 * u.NBJ;
-        float g6[6];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) {
-            const int c = j * 6 + e;
-            float gp = u.gprior[b * Dn + c] * u.w_pose2;
-            if (u.mode == 1) gp = gp / u.nb_[c];
-            else if (u.mode == 2) gp = (gp / (u.nb_[c] - u.na[c])) * 2.0f;
-            g6[e] = gp;
-        }
-        const float dR[9] = {g6[0], g6[1], 0.f, g6[2], g6[3], 0.f, g6[4], g6[5], 0.f};
-        rodrigues_bwd(q[0], q[1], q[2], dR, gq);
-    } else {
-        const int Dn = 3 * u.NBJ;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int cc = j * 3 + c;
-            float gp = u.gprior[b * Dn + cc] * u.w_pose2;
-            if (u.mode == 1) gp = gp / u.nb_[cc];
-            else if (u.mode == 2) gp = (gp / (u.nb_[cc] - u.na[cc])) * 2.0f;
-            gq[c] = gp;
-        }
-    }
+    pose_norm_joint_bwd(u.gprior + b * Dn, j, u.w_pose2, q, j, u.mode, u.na, u.nb_, u.rot6d != 0, gq);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int idx = j * 3 + c;
@@ -337,7 +285,7 @@ __global__ void __launch_bounds__(256) k_sp_body_update(BodyUpdate u) {
         }
         q[c] = sp_adam(q[c], g, m + 3 + idx, v + 3 + idx, u.s);
     }
-    if (u.xn) sp_norm_joint(q, j, u.mode, u.na, u.nb_, u.rot6d != 0, u.xn + b * (u.rot6d ? 6 : 3) * u.NBJ);
+    if (u.xn) pose_norm_joint(q, j, u.mode, u.na, u.nb_, u.rot6d != 0, u.xn + b * Dn, j);
 }
 
 struct Scratch {
@@ -355,15 +303,6 @@ Scratch layout(char* base, int64_t B, int V, int J, int rows, int L, int Dn) {
     s.dshape = take(B * L); s.sb = take(dposer_shape_blend_scratch_floats(V, L, B)); s.xn = take(B * Dn); s.gprior = take(B * Dn); s.z = take(B * Dn);
     s.loss1 = take(64); s.dcam = take(B * 3); s.mc = take(B * 6); s.vc = take(B * 6); s.mb = take(B * P); s.vb = take(B * P);
     s.bytes = p - base;
-    return s;
-}
-
-AdamScalars adam_scalars(const dposer_smplify_args* a, int64_t stepno) {
-    // torch.optim.Adam scalars of optimiser step `stepno` (python doubles, rounded once)
-    const double bc1 = 1.0 - std::pow(a->beta1, (double)stepno), bc2 = 1.0 - std::pow(a->beta2, (double)stepno);
-    AdamScalars s;
-    s.step_size = (float)(a->lr / bc1); s.one_minus_beta1 = (float)(1.0 - a->beta1); s.beta2 = (float)a->beta2;
-    s.one_minus_beta2 = (float)(1.0 - a->beta2); s.bc2_sqrt = (float)std::sqrt(bc2); s.eps = (float)a->eps;
     return s;
 }
 
@@ -422,12 +361,12 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
     segs[a->body_segment] = a->body_pose;
     dsegs[a->orient_segment] = s.dorient;
     const int64_t P = 3 + 3 * (int64_t)NBJ + a->num_betas;
-    SP_HIP_LAUNCH(hipMemsetAsync(s.djoints, 0, (size_t)B * rows * 3 * 4, st));     // rows no keypoint maps to stay zero
-    SP_HIP_LAUNCH(hipMemsetAsync(s.dverts, 0, (size_t)B * V * 3 * 4, st));         // no loss term reads vertices
-    SP_HIP_LAUNCH(hipMemsetAsync(s.mc, 0, (size_t)B * 6 * 4, st));
-    SP_HIP_LAUNCH(hipMemsetAsync(s.vc, 0, (size_t)B * 6 * 4, st));
-    SP_HIP_LAUNCH(hipMemsetAsync(s.mb, 0, (size_t)B * P * 4, st));
-    SP_HIP_LAUNCH(hipMemsetAsync(s.vb, 0, (size_t)B * P * 4, st));
+    DP_CHECK_HIP(hipMemsetAsync(s.djoints, 0, (size_t)B * rows * 3 * 4, st));     // rows no keypoint maps to stay zero
+    DP_CHECK_HIP(hipMemsetAsync(s.dverts, 0, (size_t)B * V * 3 * 4, st));         // no loss term reads vertices
+    DP_CHECK_HIP(hipMemsetAsync(s.mc, 0, (size_t)B * 6 * 4, st));
+    DP_CHECK_HIP(hipMemsetAsync(s.vc, 0, (size_t)B * 6 * 4, st));
+    DP_CHECK_HIP(hipMemsetAsync(s.mb, 0, (size_t)B * P * 4, st));
+    DP_CHECK_HIP(hipMemsetAsync(s.vb, 0, (size_t)B * P * 4, st));
 
     FitArgs fa;
     fa.joints = s.joints; fa.rows = rows; fa.kp = a->keypoints; fa.K = K; fa.focal = a->focal_length; fa.center = a->camera_center;
@@ -446,13 +385,13 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
         DP_TRY(lbs_fwd());
         fa.log4 = a->loss_log ? a->loss_log + (int64_t)k * B * 4 : nullptr;
         hipLaunchKernelGGL(k_sp_cam_grad, dim3((unsigned)B), dim3(64), 0, st, fa, ca);
-        SP_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
         DP_TRY(dposer_lbs_backward_fold(a->body, a->lbs_ws_fwd, a->lbs_ws_bwd, a->posedirs_bwd_packed, segs, a->segment_joints_host, a->num_segments,
                                         s.jr, 1, s.vs, 1, a->skin_idx, a->skin_w, a->skin_k, a->joint_ptr, a->joint_vidx, a->joint_w, s.dverts,
                                         s.djoints, (int64_t)rows * 3, a->fold, dsegs, nullptr, nullptr, B, stream));
         hipLaunchKernelGGL(k_sp_cam_update, dim3((unsigned)ceil_div(B, 256)), dim3(256), 0, st, a->global_orient, a->cam_t, (const float*)s.dorient,
-                           (const float*)s.dcam, s.mc, s.vc, B, adam_scalars(a, k + 1));
-        SP_HIP_LAUNCH(hipGetLastError());
+                           (const float*)s.dcam, s.mc, s.vc, B, adam_scalars(a->lr, a->beta1, a->beta2, a->eps, k + 1));
+        DP_CHECK_HIP(hipGetLastError());
     }
 
     // ---- joints_conf[:, ign_joints] = 0 (smplify.py:238)
@@ -461,7 +400,7 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
     ign.n = a->n_ign;
     if (ign.n) {
         hipLaunchKernelGGL(k_sp_zero_conf, dim3((unsigned)ceil_div(B, 256)), dim3(256), 0, st, a->keypoints, B, K, ign);
-        SP_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
 
     // ---- body stage (smplify.py:240-263): a fresh Adam over [body_pose | betas | global_orient]
@@ -471,7 +410,7 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
         const int64_t nn = B * NBJ;
         hipLaunchKernelGGL(k_sp_normalize, dim3((unsigned)ceil_div(nn, 256)), dim3(256), 0, st, (const float*)a->body_pose, NBJ, a->norm_mode, a->norm_a,
                            a->norm_b, a->rot6d, s.xn, nn);
-        SP_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     for (int k = 0; k < n_body; ++k) {
         const int stage = k / a->num_iters;
@@ -482,7 +421,7 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
         if (!a->noise) {
             hipLaunchKernelGGL(k_sp_noise, dim3((unsigned)ceil_div(B * ((Dn + 3) / 4), 256)), dim3(256), 0, st, s.z, B, Dn, a->row0, a->seed,
                                a->step0 + (uint32_t)k);
-            SP_HIP_LAUNCH(hipGetLastError());
+            DP_CHECK_HIP(hipGetLastError());
         }
         // DPoser.DPoser_loss (smplify.py:93-107): sum(w (x - x0_hat)^2) / batch_size with w = 0.5 sqrt(1 + SNR)
         DP_TRY(dposer_prior_loss_tabled(a->net, a->flat_params, a->packed, a->net_ws, a->sde, s.xn, z, a->t_host[k], k, n_body, 1, a->inv_batch,
@@ -492,7 +431,7 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
         bo.nb = a->num_betas; bo.w_angle2 = wa * wa; bo.w_shape2 = ws * ws; bo.w_pose2 = wp * wp; bo.prior_loss = s.loss1; bo.reprojection = nullptr;
         fa.log4 = a->loss_log ? a->loss_log + (int64_t)(a->num_iters + k) * B * 4 : nullptr;
         hipLaunchKernelGGL(k_sp_body_grad<false>, dim3((unsigned)B), dim3(64), 0, st, fa, bo);
-        SP_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
         DP_TRY(dposer_lbs_backward_fold(a->body, a->lbs_ws_fwd, a->lbs_ws_bwd, a->posedirs_bwd_packed, segs, a->segment_joints_host, a->num_segments,
                                         s.jr, 1, s.vs, 1, a->skin_idx, a->skin_w, a->skin_k, a->joint_ptr, a->joint_vidx, a->joint_w, s.dverts,
                                         s.djoints, (int64_t)rows * 3, a->fold, dsegs, s.djrest, s.dvposed, B, stream));
@@ -501,9 +440,9 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
         u.orient = a->global_orient; u.body_pose = a->body_pose; u.shape = a->shape; u.dorient = s.dorient; u.dbody = s.dbody; u.dshape = s.dshape;
         u.gprior = s.gprior; u.m = s.mb; u.v = s.vb; u.xn = k + 1 < n_body ? s.xn : nullptr; u.na = a->norm_a; u.nb_ = a->norm_b;
         u.mode = a->norm_mode; u.rot6d = a->rot6d; u.NBJ = NBJ; u.L = L; u.nbetas = a->num_betas; u.n = B * (1 + NBJ + a->num_betas);
-        u.w_pose2 = wp * wp; u.w_angle2 = wa * wa; u.w_shape2 = ws * ws; u.inv_batch = a->inv_batch; u.s = adam_scalars(a, (int64_t)k + 1);
+        u.w_pose2 = wp * wp; u.w_angle2 = wa * wa; u.w_shape2 = ws * ws; u.inv_batch = a->inv_batch; u.s = adam_scalars(a->lr, a->beta1, a->beta2, a->eps, k + 1);
         hipLaunchKernelGGL(k_sp_body_update, dim3((unsigned)ceil_div(u.n, 256)), dim3(256), 0, st, u);
-        SP_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
 
     // ---- reprojection_loss of the final parameters with the zeroed confidences (smplify.py:266-277)
@@ -514,6 +453,6 @@ extern "C" int dposer_smplify_optimize(const dposer_smplify_args* a, void* strea
     bo.sigma2 = a->sigma * a->sigma; bo.reprojection = a->reprojection;
     fa.log4 = nullptr;
     hipLaunchKernelGGL(k_sp_body_grad<true>, dim3((unsigned)B), dim3(64), 0, st, fa, bo);
-    SP_HIP_LAUNCH(hipGetLastError());
+    DP_CHECK_HIP(hipGetLastError());
     return DPOSER_OK;
 }

@@ -18,14 +18,7 @@
 #include <string>
 
 #include "common.h"
-#include "rot_dev.h"
-
-#define TK_HIP_LAUNCH(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return dposer_set_error(DPOSER_ERR_HIP, std::string(__func__) + ": " + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
+#include "optim_dev.h"
 
 namespace {
 
@@ -38,17 +31,11 @@ __device__ __forceinline__ float block_sum(float v, float* red) {      // 256 th
     return red[0] + red[1] + red[2] + red[3];
 }
 
-// offline_normalize(from_axis=True) for the axis-angle representation (AMASS.py:126-137): mode 0 identity, 1 z-score (a = mean,
-// b = std), 2 min-max (a = min, b = max)
-__device__ __forceinline__ float md_norm(float p, int mode, const float* a, const float* b, int c) {
-    if (mode == 1) return (p - a[c]) / b[c];
-    if (mode == 2) return 2.0f * (p - a[c]) / (b[c] - a[c]) - 1.0f;
-    return p;
-}
+// offline_normalize(from_axis=True) for the axis-angle representation (optim_dev.h pose_norm)
 __global__ void __launch_bounds__(256) k_md_normalize(const float* pose, const float* a, const float* b, int mode, float* xn, int64_t n, int D) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    xn[i] = md_norm(pose[i], mode, a, b, (int)(i % D));
+    xn[i] = pose_norm(pose[i], mode, a, b, (int)(i % D));
 }
 
 // offline_normalize(from_axis=True) for rot_rep = 'rot6d' (AMASS.py:126-137 -> lib/utils/transforms.py:238-255): every joint's axis-angle
@@ -58,12 +45,7 @@ __global__ void __launch_bounds__(256) k_md_normalize6d(const float* pose, const
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_joints) return;
     const int j = (int)(i % J);
-    const float* r = pose + i * 3;
-    const Mat3 R = rodrigues(r[0], r[1], r[2]);
-    const float six[6] = {R.m[0], R.m[1], R.m[3], R.m[4], R.m[6], R.m[7]};
-    float* o = xn + i * 6;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) o[e] = md_norm(six[e], mode, a, b, j * 6 + e);
+    pose_norm_joint(pose + i * 3, j, mode, a, b, true, xn + i * 6, 0);
 }
 
 // temporal term (:253-255): temp = mean over (T-1, V) of ||v[t] - v[t+1]||; d temp / d v[t] = (u_t - u_{t-1}) / ((T-1) V),
@@ -235,32 +217,28 @@ __global__ void __launch_bounds__(256) k_md_temp_log(const float* part4, int n_t
     if (threadIdx.x == 0) log3[3 * (int64_t)blockIdx.x] = temp;
 }
 
-// d pose = LBS gradient + w_prior * normalise^T(d prior / d x_n); torch.optim.Adam (single-tensor arithmetic, as k_completion_update)
+// d pose = LBS gradient + w_prior * normalise^T(d prior / d x_n); torch.optim.Adam (optim_dev.h adam_step)
 struct MdUpdateArgs {
     float* pose; float* m; float* v;
     float* xn_next;      // axis-angle form, optional: the NEXT step's normalised pose (k_md_normalize's expression on the value just written: one launch less per step)
     const float* dpose; const float* gprior; const float* a; const float* b;
     int mode, D;
     int64_t n;
-    float w_prior, step_size, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps;
+    float w_prior;
+    AdamScalars s;
 };
 __global__ void __launch_bounds__(256) k_md_update(MdUpdateArgs u) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= u.n) return;
     const int c = (int)(i % u.D);
-    float gp = u.gprior[i] * u.w_prior;
-    if (u.mode == 1) gp = gp / u.b[c];
-    else if (u.mode == 2) gp = (gp / (u.b[c] - u.a[c])) * 2.0f;
+    const float gp = pose_norm_bwd(u.gprior[i] * u.w_prior, u.mode, u.a, u.b, c);
     const float g = u.dpose[i] + gp;
     float m = u.m[i], v = u.v[i];
-    m = m + (g - m) * u.one_minus_beta1;
-    v = v * u.beta2 + u.one_minus_beta2 * (g * g);
-    const float denom = sqrtf(v) / u.bc2_sqrt + u.eps;
-    const float p = u.pose[i] - u.step_size * (m / denom);
+    const float p = adam_step(u.pose[i], g, m, v, u.s);
     u.pose[i] = p;
     u.m[i] = m;
     u.v[i] = v;
-    if (u.xn_next) u.xn_next[i] = md_norm(p, u.mode, u.a, u.b, c);
+    if (u.xn_next) u.xn_next[i] = pose_norm(p, u.mode, u.a, u.b, c);
 }
 
 // the same update for rot_rep = 'rot6d': the prior gradient arrives in the 6 J normalised coordinates; normalise^T, then the
@@ -270,28 +248,15 @@ __global__ void __launch_bounds__(256) k_md_update6d(MdUpdateArgs u, int64_t n_j
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_joints) return;
     const int j = (int)(i % J);
-    float g6[6];
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-        const int c = j * 6 + e;
-        float gp = u.gprior[i * 6 + e] * u.w_prior;
-        if (u.mode == 1) gp = gp / u.b[c];
-        else if (u.mode == 2) gp = (gp / (u.b[c] - u.a[c])) * 2.0f;
-        g6[e] = gp;
-    }
-    const float dR[9] = {g6[0], g6[1], 0.f, g6[2], g6[3], 0.f, g6[4], g6[5], 0.f};
     float* q = u.pose + i * 3;
     float gq[3];
-    rodrigues_bwd(q[0], q[1], q[2], dR, gq);
+    pose_norm_joint_bwd(u.gprior + i * 6, 0, u.w_prior, q, j, u.mode, u.a, u.b, true, gq);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int64_t k = i * 3 + c;
         const float g = u.dpose[k] + gq[c];
         float m = u.m[k], v = u.v[k];
-        m = m + (g - m) * u.one_minus_beta1;
-        v = v * u.beta2 + u.one_minus_beta2 * (g * g);
-        const float denom = sqrtf(v) / u.bc2_sqrt + u.eps;
-        q[c] = q[c] - u.step_size * (m / denom);
+        q[c] = adam_step(q[c], g, m, v, u.s);
         u.m[k] = m;
         u.v[k] = v;
     }
@@ -311,6 +276,41 @@ Scratch layout(char* base, int64_t T, int D, int V, int n_joint_rows, int n_part
     s.dpose = take(T * D); s.part = take((int64_t)n_part * 4);      // (x 4: per-wave sums when the temporal term is formed inside the skinning backward)
     s.bytes = p - base;
     return s;
+}
+
+// Where a step forms the temporal term's gradient:
+//   TEMPORAL_TWO_KERNEL   dposer_lbs_forward writes the vertices, k_md_vert_grad reads them back
+//   TEMPORAL_FUSED_SKIN   skinning and the term's gradient in one pass (dposer_lbs_forward_temporal_grad): no vertices in HBM.  A workgroup
+//                         of the fused kernel walks >= 10 frames one after the other: measured 0.60 vs 0.67 ms per step at 8 sequences of 60
+//                         frames, a tie at one -- hence the default from 4 sequences per call
+//   TEMPORAL_IN_BACKWARD  inside the skinning backward, from the forward's transforms and offsets (dposer_lbs_backward_temporal): no skinning
+//                         kernel, no vertices and no vertex gradient in HBM (k_skin_temporal wrote 967 MB at 7680 frames that k_skin_bwd_mfma
+//                         read back).  Measured, profiles/r06_md_ab.md: 2.63 -> 2.51 ms per step at 7680 frames, 0.83 -> 0.79 at 1920, a loss
+//                         at 480 -- the backward kernel is VALU-bound once it skins three frames per pose -- hence the default from 960 frames
+// With fused_ok = skin_k == 4 && F <= 4096 && n_seq <= 16384 and in_bwd_ok = dposer_lbs_temporal_in_backward_ok(body, skin_k, T), the first
+// row that applies decides:
+//   DPOSER_MD_IEEE_DIV=1                  two-kernel with IEEE divisions (the A/B switch exists in that form only), whatever else is set
+//   DPOSER_MD_FUSED_TEMPORAL=0            two-kernel
+//   DPOSER_MD_FUSED_TEMPORAL=1            fused skinning if fused_ok, else two-kernel                                  (neither MIN is read)
+//   DPOSER_MD_FUSED_TEMPORAL=2            in the backward if in_bwd_ok, else fused skinning if fused_ok, else two-kernel (neither MIN is read)
+//   otherwise (unset, any other value)    in the backward if in_bwd_ok && T >= DPOSER_MD_TEMPORAL_IN_BWD_MIN_FRAMES (default 960),
+//                                         else fused skinning if fused_ok && n_seq >= DPOSER_MD_FUSED_TEMPORAL_MIN_SEQ (default 4),
+//                                         else two-kernel
+// (only the first character of the two switches counts; the environment is read on every call, once per variable)
+enum TemporalHome { TEMPORAL_TWO_KERNEL, TEMPORAL_FUSED_SKIN, TEMPORAL_IN_BACKWARD };
+TemporalHome temporal_home(int skin_k, int64_t F, int64_t n_seq, int64_t T, bool in_bwd_ok, bool* ieee_div) {
+    const char* e = getenv("DPOSER_MD_FUSED_TEMPORAL");
+    const char* d = getenv("DPOSER_MD_IEEE_DIV");
+    const char* mf = getenv("DPOSER_MD_TEMPORAL_IN_BWD_MIN_FRAMES");
+    const char* ms = getenv("DPOSER_MD_FUSED_TEMPORAL_MIN_SEQ");
+    const char force = e ? e[0] : '\0';
+    const bool forced = force == '1' || force == '2';
+    *ieee_div = d && d[0] == '1';
+    if (*ieee_div || force == '0') return TEMPORAL_TWO_KERNEL;
+    if (force != '1' && in_bwd_ok && (forced || T >= (mf ? atoll(mf) : 960))) return TEMPORAL_IN_BACKWARD;
+    const bool fused_ok = skin_k == 4 && F <= 4096 && n_seq <= 16384;
+    if (fused_ok && (forced || n_seq >= (ms ? atoll(ms) : 4))) return TEMPORAL_FUSED_SKIN;
+    return TEMPORAL_TWO_KERNEL;
 }
 
 }   // namespace
@@ -360,33 +360,11 @@ extern "C" int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* 
     segs[a->body_segment] = a->pose;
     dsegs[a->body_segment] = s.dpose;
     // d joints: only the observed joints' columns are ever non-zero
-    TK_HIP_LAUNCH(hipMemsetAsync(s.djoints, 0, (size_t)T * a->joint_rows * 3 * 4, st));
+    DP_CHECK_HIP(hipMemsetAsync(s.djoints, 0, (size_t)T * a->joint_rows * 3 * 4, st));
 
-    // DPOSER_MD_FUSED_TEMPORAL = 0 / 1 forces the two-kernel / fused form of skinning + temporal gradient (default: fused from
-    // DPOSER_MD_FUSED_TEMPORAL_MIN_SEQ = 4 sequences per call: a workgroup of the fused kernel walks >= 10 frames one after the other;
-    // measured 0.60 vs 0.67 ms per step at 8 sequences of 60 frames, a tie at one)
-    bool fused_temporal = a->skin_k == 4 && F <= 4096 && n_seq <= 16384;
-    // DPOSER_MD_FUSED_TEMPORAL = 2 (default from 960 frames per call, where dposer_lbs_temporal_in_backward_ok): the temporal term's
-    // gradient is formed INSIDE the skinning backward from the forward's transforms and offsets -- no skinning kernel, no vertices and no
-    // vertex gradient in HBM (k_skin_temporal wrote 967 MB at 7680 frames that k_skin_bwd_mfma read back)
-    // (measured, profiles/r06_md_ab.md: 2.63 -> 2.51 ms per step at 7680 frames, 0.83 -> 0.79 at 1920, a loss at 480 -- the backward kernel is
-    //  VALU-bound once it skins three frames per pose -- hence DPOSER_MD_TEMPORAL_IN_BWD_MIN_FRAMES = 960)
-    bool temporal_in_backward = dposer_lbs_temporal_in_backward_ok(a->body, a->skin_k, T) != 0;
-    {
-        const char* m = getenv("DPOSER_MD_TEMPORAL_IN_BWD_MIN_FRAMES");
-        const char* e = getenv("DPOSER_MD_FUSED_TEMPORAL");
-        if (!(e && e[0] == '2') && T < (m ? atoll(m) : 960)) temporal_in_backward = false;
-    }
-    bool ieee_div = false;
-    { const char* e = getenv("DPOSER_MD_IEEE_DIV"); ieee_div = e && e[0] == '1'; }
-    if (ieee_div) { fused_temporal = false; temporal_in_backward = false; }      // (the A/B switch exists in the two-kernel form only)
-    {
-        const char* e = getenv("DPOSER_MD_FUSED_TEMPORAL");
-        const char* m = getenv("DPOSER_MD_FUSED_TEMPORAL_MIN_SEQ");
-        if (e && e[0] == '0') { fused_temporal = false; temporal_in_backward = false; }
-        else if (e && e[0] == '1') temporal_in_backward = false;
-        else if (!(e && e[0] == '2')) fused_temporal = fused_temporal && n_seq >= (m ? atoll(m) : 4);
-    }
+    bool ieee_div;
+    const TemporalHome home = temporal_home(a->skin_k, F, n_seq, T, dposer_lbs_temporal_in_backward_ok(a->body, a->skin_k, T) != 0, &ieee_div);
+    const bool temporal_in_backward = home == TEMPORAL_IN_BACKWARD, fused_temporal = home == TEMPORAL_FUSED_SKIN;
 
     // time-bias rows of all steps: two small GEMMs once instead of per step
     if (a->n_steps > 0) DP_TRY(dposer_prior_table_build_sde(a->net, a->flat_params, a->packed, a->net_ws, a->sde, a->t_host, a->n_steps, a->freq, T, stream));
@@ -394,7 +372,7 @@ extern "C" int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* 
         if (rot6d) hipLaunchKernelGGL(k_md_normalize6d, dim3((unsigned)ceil_div(n / 3, 256)), dim3(256), 0, st, (const float*)a->pose, a->norm_a, a->norm_b, a->norm_mode, s.xn, n / 3, D / 3);
         else if (k == 0) hipLaunchKernelGGL(k_md_normalize, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const float*)a->pose, a->norm_a, a->norm_b, a->norm_mode, s.xn, n, D);
         // (axis-angle, k > 0: the previous step's update kernel has written s.xn already)
-        TK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
         DP_TRY(dposer_prior_loss_tabled(a->net, a->flat_params, a->packed, a->net_ws, a->sde, s.xn, a->noise ? a->noise + (int64_t)k * n_net : nullptr,
                                         a->t_host[k], k, a->n_steps, a->weighted, 1.0f / (float)F, nullptr, s.gprior, s.loss1, a->seed,
                                         a->step0 + (uint32_t)k, a->sigmas, T, stream));
@@ -415,7 +393,7 @@ extern "C" int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* 
                                       s.verts, s.joints, T, stream));
             if (ieee_div) hipLaunchKernelGGL(k_md_vert_grad<true>, dim3((unsigned)vb, (unsigned)T), dim3(256), 0, st, (const float*)s.verts, s.dverts, s.part, (int)F, V, c_temp);
             else hipLaunchKernelGGL(k_md_vert_grad<false>, dim3((unsigned)vb, (unsigned)T), dim3(256), 0, st, (const float*)s.verts, s.dverts, s.part, (int)F, V, c_temp);
-            TK_HIP_LAUNCH(hipGetLastError());
+            DP_CHECK_HIP(hipGetLastError());
         }
         if (a->joints_conf || a->obs_rows) {      // partial observations: confidences and / or a joint list (neither: the kernel and the bits of every call before them)
             auto kern = a->joints_conf ? (a->obs_rows ? k_md_joint_obs<true, true> : k_md_joint_obs<true, false>) : k_md_joint_obs<false, true>;
@@ -427,7 +405,7 @@ extern "C" int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* 
         hipLaunchKernelGGL(k_md_joint, dim3((unsigned)n_seq), dim3(256), 0, st, (const float*)s.joints, (int64_t)a->joint_rows * 3, a->joints_obs, s.djoints,
                            (int)F, a->n_obs_joints, a->w_data_host[k], (const float*)s.part, temporal_in_backward ? 0 : vb * (int)F,
                            1.0f / ((float)(F - 1) * (float)V), (const float*)s.loss1, a->loss_log ? a->loss_log + 3 * (int64_t)k * n_seq : nullptr);
-        TK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
         if (temporal_in_backward) {
             DP_TRY(dposer_lbs_backward_temporal(a->body, a->lbs_ws_fwd, a->lbs_ws_bwd, a->posedirs_bwd_packed, segs, a->segment_joints_host, a->num_segments,
                                                 a->j_rest, a->rest_batched, a->v_shaped, a->rest_batched, a->skin_idx, a->skin_w, a->skin_k, a->joint_ptr,
@@ -435,24 +413,20 @@ extern "C" int dposer_motion_denoise_optimize(const dposer_motion_denoise_args* 
             if (a->loss_log) {
                 hipLaunchKernelGGL(k_md_temp_log, dim3((unsigned)n_seq), dim3(256), 0, st, (const float*)s.part, vb * (int)F, 1.0f / ((float)(F - 1) * (float)V),
                                    a->loss_log + 3 * (int64_t)k * n_seq);
-                TK_HIP_LAUNCH(hipGetLastError());
+                DP_CHECK_HIP(hipGetLastError());
             }
         } else
         DP_TRY(dposer_lbs_backward(a->body, a->lbs_ws_fwd, a->lbs_ws_bwd, a->posedirs_bwd_packed, segs, a->segment_joints_host, a->num_segments, a->j_rest,
                                    a->rest_batched, a->v_shaped, a->rest_batched, a->skin_idx, a->skin_w, a->skin_k, a->joint_ptr, a->joint_vidx, a->joint_w,
                                    s.dverts, s.djoints, (int64_t)a->joint_rows * 3, dsegs, nullptr, nullptr, T, stream));
-        // torch.optim.Adam scalars of optimiser step adam_step0 + k + 1 (python doubles, rounded once)
-        const double stepno = (double)a->adam_step0 + k + 1;
-        const double bc1 = 1.0 - std::pow(a->beta1, stepno), bc2 = 1.0 - std::pow(a->beta2, stepno);
         MdUpdateArgs u;
         u.xn_next = (!rot6d && k + 1 < a->n_steps) ? s.xn : nullptr;
         u.pose = a->pose; u.m = a->adam_m; u.v = a->adam_v; u.dpose = s.dpose; u.gprior = s.gprior; u.a = a->norm_a; u.b = a->norm_b;
         u.mode = a->norm_mode; u.D = D; u.n = n; u.w_prior = a->w_prior_host[k];
-        u.step_size = (float)(a->lr / bc1); u.one_minus_beta1 = (float)(1.0 - a->beta1); u.beta2 = (float)a->beta2;
-        u.one_minus_beta2 = (float)(1.0 - a->beta2); u.bc2_sqrt = (float)std::sqrt(bc2); u.eps = (float)a->eps;
+        u.s = adam_scalars(a->lr, a->beta1, a->beta2, a->eps, (double)a->adam_step0 + k + 1);
         if (rot6d) hipLaunchKernelGGL(k_md_update6d, dim3((unsigned)ceil_div(n / 3, 256)), dim3(256), 0, st, u, n / 3, D / 3);
         else hipLaunchKernelGGL(k_md_update, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, u);
-        TK_HIP_LAUNCH(hipGetLastError());
+        DP_CHECK_HIP(hipGetLastError());
     }
     return DPOSER_OK;
 }

@@ -7,8 +7,6 @@ network evaluation (x0_hat is detached in the reference, so no gradient ever flo
 network), Tweedie estimate, weighted L2 -- with the analytic gradient 2 w (x_0 - x0_hat)/n returned
 to autograd.
 """
-import ctypes as C
-
 import torch
 from torch import nn
 
@@ -17,27 +15,23 @@ from .algorithms.advanced import sde_lib
 from .algorithms.advanced.model import ScoreModelFC
 from .algorithms.ema import ExponentialMovingAverage
 from .dataset.AMASS import N_POSES, Posenormalizer
+from .tasks._fused import ScoreNetCall, float_array
 
 
 class _PriorLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, model, sde, t, weighted, inv_n, z, seed, step, continuous=True):
         _C.require_gpu(x0, "prior-loss input")
-        eng = model._engine()
-        flat = model.flat_params()
-        packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
         B = x0.shape[0]
-        ws = eng.workspace(B, _C.WS_SHARED_T, 1, x0.device)
+        net = ScoreNetCall(model, sde, continuous, B, 1, x0.device)
         x = x0.detach().contiguous().float()
         grad = torch.empty_like(x)
         x0_hat = torch.empty_like(x)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        desc = sde_lib.sde_desc(sde, continuous)
         zz = None if z is None else z.contiguous().float()
-        _C.check(eng.lib.dposer_prior_loss(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), _C.ptr(x), _C.ptr(zz), float(t),
-                                           1 if weighted else 0, float(inv_n), _C.ptr(x0_hat), _C.ptr(grad), _C.ptr(loss), int(seed),
-                                           int(step) & 0xFFFFFFFF, _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B,
-                                           _C.stream_ptr()), "dposer_prior_loss")
+        _C.check(net.eng.lib.dposer_prior_loss(*net.head(), _C.ptr(x), _C.ptr(zz), float(t), 1 if weighted else 0, float(inv_n), _C.ptr(x0_hat),
+                                               _C.ptr(grad), _C.ptr(loss), int(seed), int(step) & 0xFFFFFFFF, *net.tail(), B, _C.stream_ptr()),
+                 "dposer_prior_loss")
         ctx.save_for_backward(grad)
         ctx.x0_hat = x0_hat
         return loss[0]
@@ -87,49 +81,36 @@ def _fused_variant_desc(model, sde, continuous):
     return sde_lib.sde_desc(sde, True)
 
 
-def _call_setup(model, x0, n_rows):
-    eng = model._engine()
-    flat = model.flat_params()
-    packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
-    ws = eng.workspace(x0.shape[0], _C.WS_SHARED_T, n_rows, x0.device)
-    return eng, flat, packed, ws
-
-
 def multi_step_prior_eval(model, sde, x0, traj, *, weighted, inv_n, z=None, seed=0, step=0, x0_hat=None, grad=None):
     """One ``dposer_prior_loss_multi`` call along the times ``traj`` (N + 1 python floats): returns ``(loss [1], grad, x0_hat)``, all
     device tensors.  ``x0_hat`` / ``grad``: optional contiguous fp32 [B, D] tensors to write into."""
     _C.require_gpu(x0, "prior-loss input")
     n_steps = len(traj) - 1
-    eng, flat, packed, ws = _call_setup(model, x0, n_steps)
+    net = ScoreNetCall(model, sde, True, x0.shape[0], n_steps, x0.device)
     x = x0.detach().contiguous().float()
     B = x.shape[0]
     grad = torch.empty_like(x) if grad is None else grad
     x0_hat = torch.empty_like(x) if x0_hat is None else x0_hat
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     zz = None if z is None else z.detach().to(x.device).contiguous().float()
-    desc = sde_lib.sde_desc(sde, True)
-    t_host = (C.c_float * (n_steps + 1))(*traj)
-    _C.check(eng.lib.dposer_prior_loss_multi(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), _C.ptr(x), _C.ptr(zz), t_host,
-                                             n_steps, 1 if weighted else 0, float(inv_n), _C.ptr(x0_hat), _C.ptr(grad), _C.ptr(loss), int(seed),
-                                             int(step) & 0xFFFFFFFF, _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B,
-                                             _C.stream_ptr()), "dposer_prior_loss_multi")
+    _C.check(net.eng.lib.dposer_prior_loss_multi(*net.head(), _C.ptr(x), _C.ptr(zz), float_array(traj), n_steps, 1 if weighted else 0, float(inv_n),
+                                                 _C.ptr(x0_hat), _C.ptr(grad), _C.ptr(loss), int(seed), int(step) & 0xFFFFFFFF, *net.tail(), B,
+                                                 _C.stream_ptr()), "dposer_prior_loss_multi")
     return loss, grad, x0_hat
 
 
 def red_diff_eval(model, sde, x0, t, *, z=None, seed=0, step=0, eps_pred=None, grad=None):
     """One ``dposer_prior_red_diff`` call: returns ``(loss [1], grad, eps_pred)``, all device tensors; ``eps_pred`` / ``grad`` as above."""
     _C.require_gpu(x0, "RED-Diff input")
-    eng, flat, packed, ws = _call_setup(model, x0, 1)
+    net = ScoreNetCall(model, sde, True, x0.shape[0], 1, x0.device)
     x = x0.detach().contiguous().float()
     B = x.shape[0]
     grad = torch.empty_like(x) if grad is None else grad
     eps_pred = torch.empty_like(x) if eps_pred is None else eps_pred
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     zz = None if z is None else z.detach().to(x.device).contiguous().float()
-    desc = sde_lib.sde_desc(sde, True)
-    _C.check(eng.lib.dposer_prior_red_diff(eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(desc), _C.ptr(x), _C.ptr(zz), float(t),
-                                           1.0 / float(B), _C.ptr(eps_pred), _C.ptr(grad), _C.ptr(loss), int(seed), int(step) & 0xFFFFFFFF,
-                                           _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B, _C.stream_ptr()),
+    _C.check(net.eng.lib.dposer_prior_red_diff(*net.head(), _C.ptr(x), _C.ptr(zz), float(t), 1.0 / float(B), _C.ptr(eps_pred), _C.ptr(grad),
+                                               _C.ptr(loss), int(seed), int(step) & 0xFFFFFFFF, *net.tail(), B, _C.stream_ptr()),
              "dposer_prior_red_diff")
     return loss, grad, eps_pred
 

@@ -18,6 +18,7 @@ from torch import nn
 from .. import _C
 from ..algorithms.advanced import sde_lib
 from ..prior import prior_loss
+from ._fused import ScoreNetCall, float_array
 
 
 class DPoserComp:
@@ -72,28 +73,24 @@ class DPoserComp:
         if self._fused_supported():
             _C.require_gpu(observation, "completion observation")
             model = self.model
-            eng = model._engine()
-            flat = model.flat_params()
-            packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)      # once per loop
             B, D = observation.shape
-            ws = eng.workspace(B, _C.WS_SHARED_T, total_steps, observation.device)
+            net = ScoreNetCall(model, self.sde, bool(getattr(self, "continuous", True)), B, total_steps, observation.device)   # (packed once per loop)
             obs = observation.detach().contiguous().float()
             msk = mask.detach().contiguous().float()
             x = obs.clone()
             m, v = torch.zeros_like(x), torch.zeros_like(x)
             its = [s // steps_per_iter for s in range(total_steps)]
-            t_host = (C.c_float * total_steps)(*[float(timesteps[q]) for q in quan])
+            t_host = float_array(timesteps[q] for q in quan)
             # the reference passes quan_t positionally into `weighted` (completion.py:196): weighted = bool(quan_t)
             wflag = (C.c_int32 * total_steps)(*[1 if q else 0 for q in quan])
-            w_prior = (C.c_float * total_steps)(*[float(weights["dposer"](1.0, it)) for it in its])
-            w_data = (C.c_float * total_steps)(*[float(weights["data"](1.0, it)) for it in its])
+            w_prior = float_array(weights["dposer"](1.0, it) for it in its)
+            w_data = float_array(weights["data"](1.0, it) for it in its)
             nz = None if noise is None else noise.detach().contiguous().float()
             step0 = self._calls + 1
             self._calls += total_steps
-            _C.check(eng.lib.dposer_completion_optimize(
-                eng.h, _C.ptr(flat), _C.ptr(packed), _C.ptr(ws), C.byref(sde_lib.sde_desc(self.sde, bool(getattr(self, "continuous", True)))), _C.ptr(x), _C.ptr(obs), _C.ptr(msk),
-                _C.ptr(m), _C.ptr(v), t_host, wflag, w_prior, w_data, total_steps, float(lr), 0.9, 0.999, 1e-8, _C.ptr(nz),
-                int(model._rng_seed + 29), int(step0) & 0xFFFFFFFF, _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B, _C.stream_ptr()),
+            _C.check(net.eng.lib.dposer_completion_optimize(
+                *net.head(), _C.ptr(x), _C.ptr(obs), _C.ptr(msk), _C.ptr(m), _C.ptr(v), t_host, wflag, w_prior, w_data, total_steps, float(lr),
+                0.9, 0.999, 1e-8, _C.ptr(nz), int(model._rng_seed + 29), int(step0) & 0xFFFFFFFF, *net.tail(), B, _C.stream_ptr()),
                 "dposer_completion_optimize")
             return observation * mask + x * (1.0 - mask)
         x = observation.clone().detach().requires_grad_(True)

@@ -28,6 +28,7 @@ from .. import _C
 from ..algorithms.advanced import sde_lib
 from ..prior import prior_loss, red_diff
 from ..utils.misc import gaussian_smoothing
+from ._fused import BodyTables, ScoreNetCall, float_array, normalizer_tables
 
 
 def _axis_angle_to_rot6d_autograd(aa):
@@ -176,11 +177,8 @@ class MotionDenoise:
         dev = pose.device
         T, D = pose.shape
         n_steps = len(t_list)
-        eng = model._engine()
-        flat = model.flat_params()
-        packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)      # once per loop
-        ws = eng.workspace(T, _C.WS_SHARED_T, n_steps, dev)
-        lib, h = _C.lib(), core._handle()
+        net = ScoreNetCall(model, self.sde, bool(getattr(self, "continuous", True)), T, n_steps, dev)      # (the weights are packed once per loop)
+        eng, lib = net.eng, _C.lib()
         F = int(frames_per_sequence) if frames_per_sequence else T
         n_seq = T // F
         if betas is None:
@@ -194,13 +192,9 @@ class MotionDenoise:
         v_shaped, j_rest = v_shaped.contiguous(), j_rest.contiguous()
         if batched and v_shaped.shape[0] == 1 and T > 1:
             batched = False                                        # [1, V, 3] / [1, J, 3] read as the shared [V, 3] / [J, 3]
-        names = [name for name, _ in core.segments]
-        segj = (C.c_int32 * len(names))(*[nj for _, nj in core.segments])
-        jptr, jvidx, jw = core.joint_csr()
-        u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
-        ws_f, ws_b = u8(lib.dposer_lbs_workspace_bytes(h, T)), u8(lib.dposer_lbs_backward_workspace_bytes(h, T))
-        rows = core.J + core.n_extra + core.n_lmk
-        scratch = u8(lib.dposer_motion_denoise_scratch_bytes(T, D, core.V, rows))
+        body = BodyTables(core, landmarks=True)
+        body_fields = body.fields(T, dev)
+        scratch = torch.empty(int(lib.dposer_motion_denoise_scratch_bytes(T, D, core.V, body.rows)), dtype=torch.uint8, device=dev)
         m, v = torch.zeros_like(pose), torch.zeros_like(pose)
         log = torch.zeros(n_steps, n_seq, 3, dtype=torch.float32, device=dev)
         rot6d = getattr(nz, "rot_rep", "axis") == "rot6d"          # the network sees 6 J coordinates; the optimised pose stays axis-angle
@@ -213,34 +207,19 @@ class MotionDenoise:
             raise ValueError(f"joints_conf must be {list(obs.shape[:2])}, got {list(conf_d.shape)}")
         if rows_d is not None and (rows_d.numel() != obs.shape[1] or min(obs_rows) < 0 or max(obs_rows) >= core.J or len(set(obs_rows)) != len(obs_rows)):
             raise ValueError(f"obs_joints must be {obs.shape[1]} distinct tree joints in [0, {core.J}), got {list(obs_rows)}")
-        if not nz.normalize:
-            mode, na, nb = 0, None, None
-        elif nz.min_max:
-            mode, (na, nb) = 2, nz._stats(nz.min_poses, nz.max_poses, pose)
-        else:
-            mode, (na, nb) = 1, nz._stats(nz.mean_poses, nz.std_poses, pose)
-        if mode:
-            na, nb = na.reshape(-1).contiguous().float(), nb.reshape(-1).contiguous().float()
+        mode, na, nb = normalizer_tables(nz, pose)
         nzs = None if noise is None else noise.detach().contiguous().float()
         if nzs is not None and tuple(nzs.shape) != (n_steps, T, eng.D):
             # the C loop indexes the noise as noise + k * T * D_net: [steps, T, 6 J] with rot_rep = 'rot6d', [steps, T, 3 J] otherwise
             raise _C.DPoserHipError(f"noise must be [n_steps, frames, network inputs] = {(n_steps, T, eng.D)}, got {tuple(nzs.shape)}")
-        fl = lambda xs: (C.c_float * n_steps)(*[float(x) for x in xs])
         step0 = self._calls + 1
         self._calls += n_steps
-        desc = sde_lib.sde_desc(self.sde, bool(getattr(self, "continuous", True)))
         a = _C.MotionDenoiseArgs(
-            net=eng.h, flat_params=_C.ptr(flat), packed=_C.ptr(packed), net_ws=_C.ptr(ws), sde=C.pointer(desc), freq=_C.ptr(eng.freq(dev, self.model._fourier_W())),
-            sigmas=_C.ptr(model.sigmas), body=h, lbs_ws_fwd=_C.ptr(ws_f), lbs_ws_bwd=_C.ptr(ws_b), posedirs_packed=_C.ptr(core._packed_posedirs()),
-            posedirs_bwd_packed=_C.ptr(core._packed_posedirs_bwd()), j_rest=_C.ptr(j_rest), v_shaped=_C.ptr(v_shaped),
-            rest_batched=1 if batched else 0, skin_idx=_C.ptr(core.skin_idx), skin_w=_C.ptr(core.skin_w), skin_k=int(core.skin_idx.shape[1]),
-            joint_ptr=_C.ptr(jptr), joint_vidx=_C.ptr(jvidx), joint_w=_C.ptr(jw), extra_vertex_ids=_C.ptr(core.extra_vertex_ids),
-            lmk_tri=_C.ptr(core.lmk_tri), lmk_bary=_C.ptr(core.lmk_bary_coords), segment_joints_host=segj, num_segments=len(names),
-            body_segment=names.index("body_pose"), num_vertices=core.V, num_joints=core.J, joint_rows=rows, frames=T, frames_per_sequence=F,
-            pose=_C.ptr(pose),
+            **net.fields(), **body_fields, j_rest=_C.ptr(j_rest), v_shaped=_C.ptr(v_shaped), rest_batched=1 if batched else 0,
+            frames=T, frames_per_sequence=F, pose=_C.ptr(pose),
             adam_m=_C.ptr(m), adam_v=_C.ptr(v), joints_obs=_C.ptr(obs), n_obs_joints=int(obs.shape[1]), norm_mode=mode, norm_a=_C.ptr(na),
-            norm_b=_C.ptr(nb), n_steps=n_steps, weighted=0, t_host=fl(t_list), w_temp_host=fl(weights["temp"](1.0, it) for it in its),
-            w_data_host=fl(weights["data"](1.0, it) for it in its), w_prior_host=fl(weights["dposer"](1.0, it) for it in its),
+            norm_b=_C.ptr(nb), n_steps=n_steps, weighted=0, t_host=float_array(t_list), w_temp_host=float_array(weights["temp"](1.0, it) for it in its),
+            w_data_host=float_array(weights["data"](1.0, it) for it in its), w_prior_host=float_array(weights["dposer"](1.0, it) for it in its),
             lr=0.03, beta1=0.9, beta2=0.999, eps=1e-8, adam_step0=0, step0=int(step0) & 0xFFFFFFFF, seed=int(model._rng_seed + 31),
             noise=_C.ptr(nzs), scratch=_C.ptr(scratch), loss_log=_C.ptr(log), rot6d=1 if rot6d else 0,
             joints_conf=_C.ptr(conf_d), obs_rows=_C.ptr(rows_d))

@@ -19,6 +19,7 @@ from .. import _C
 from ..algorithms.advanced import sde_lib
 from ..body_model import constants
 from ..body_model.fitting_losses import body_fitting_loss, camera_fitting_loss
+from ._fused import BodyTables, ScoreNetCall, float_array, normalizer_tables
 
 _MAX_PER_CALL = 65535        # dposer_smplify_optimize: one grid row per pose in the skinning kernels
 
@@ -212,24 +213,16 @@ class SMPLify:
         reproj = torch.empty(B, kp.shape[1], dtype=torch.float32, device=dev)
         p = self.pose_prior
         model, nz = p.model, p.Normalizer
-        eng = model._engine()
-        flat = model.flat_params()
-        packed = eng.packed(flat, with_backward=False, force=not model.freeze_packed)
-        rot6d = getattr(nz, "rot_rep", "axis") == "rot6d"
-        Dn = eng.D
         n_body = len(t_list)
+        net = ScoreNetCall(model, p.sde, bool(getattr(p, "continuous", True)), None, max(1, n_body), dev)      # (its workspace: per group, below)
+        rot6d = getattr(nz, "rot_rep", "axis") == "rot6d"
+        Dn = net.eng.D
         if noise is not None and tuple(noise.shape) != (n_body, B, Dn):
             raise _C.DPoserHipError(f"noise must be [n_stages * num_iters, B, network inputs] = {(n_body, B, Dn)}, got {tuple(noise.shape)}")
-        if not nz.normalize:
-            mode, na, nbv = 0, None, None
-        elif nz.min_max:
-            mode, (na, nbv) = 2, nz._stats(nz.min_poses, nz.max_poses, body)
-        else:
-            mode, (na, nbv) = 1, nz._stats(nz.mean_poses, nz.std_poses, body)
-        if mode:
-            na, nbv = na.reshape(-1).contiguous().float(), nbv.reshape(-1).contiguous().float()
+        mode, na, nbv = normalizer_tables(nz, body)
         # keypoint rows of the sub core's joint output: each row's keypoints in map order (the kernels sum them without atomics)
-        rows = core.J + core.n_extra
+        tables = BodyTables(core)
+        rows = tables.rows
         m = sub_map.numpy()
         order = np.argsort(m, kind="stable")
         ptr = np.zeros(rows + 1, np.int32)
@@ -238,21 +231,15 @@ class SMPLify:
         jmap_d = sub_map.to(dev)
         ptr_d = torch.tensor(ptr, device=dev)
         ent_d = torch.tensor(order.astype(np.int32), device=dev)
-        jptr, jvidx, jw = core.joint_csr()
         fold = core.joint_fold_tables()
-        names = [n for n, _ in core.segments]
-        segj = (C.c_int32 * len(names))(*[nj for _, nj in core.segments])
         ids = lambda names_: [constants.JOINT_IDS[n] for n in names_]
         op, gt = ids(["OP RHip", "OP LHip", "OP RShoulder", "OP LShoulder"]), ids(["Right Hip", "Left Hip", "Right Shoulder", "Left Shoulder"])
         ign = list(self.ign_joints) + [0] * (8 - len(self.ign_joints))
         wts = self.loss_weights
-        fa = lambda xs: (C.c_float * max(1, len(xs)))(*[float(x) for x in xs])
-        desc = sde_lib.sde_desc(p.sde, bool(getattr(p, "continuous", True)))
         seed_v = int(model._rng_seed + 17 if seed is None else seed)
         step0 = p._calls + 1
         p._calls += n_body
-        lib, h = _C.lib(), core._handle()
-        u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
+        lib = _C.lib()
         cap = group_cap or _MAX_PER_CALL
         self.loss_log = torch.zeros(self.num_iters * (1 + self.stages), B, 4, dtype=torch.float32, device=dev)
         logs = []
@@ -260,30 +247,25 @@ class SMPLify:
             g1 = min(B, g0 + cap)
             Bg = g1 - g0
             sl = slice(g0, g1)
-            ws = eng.workspace(Bg, _C.WS_SHARED_T, max(1, n_body), dev)
-            ws_f, ws_b = u8(lib.dposer_lbs_workspace_bytes(h, Bg)), u8(lib.dposer_lbs_backward_workspace_bytes(h, Bg))
-            scratch = u8(lib.dposer_smplify_scratch_bytes(Bg, core.V, core.J, rows, L, Dn))
+            net.workspace(Bg)
+            body_fields = tables.fields(Bg, dev)
+            scratch = torch.empty(int(lib.dposer_smplify_scratch_bytes(Bg, core.V, core.J, rows, L, Dn)), dtype=torch.uint8, device=dev)
             log = torch.zeros(self.num_iters * (1 + self.stages), Bg, 4, dtype=torch.float32, device=dev)
             views = [t[sl] for t in (orient, body, shape, cam_t, kp, reproj)]
             grp = [v if g0 == 0 and g1 == B else v.contiguous() for v in views]
             nzs = None if noise is None else f32(noise[:, sl])
             focal_g, center_g, est_g = focal[sl].contiguous(), center[sl].contiguous(), cam_est[sl].contiguous()
             a = _C.SmplifyArgs(
-                net=eng.h, flat_params=_C.ptr(flat), packed=_C.ptr(packed), net_ws=_C.ptr(ws), sde=C.pointer(desc),
-                freq=_C.ptr(eng.freq(dev, model._fourier_W())), sigmas=_C.ptr(model.sigmas), body=h, lbs_ws_fwd=_C.ptr(ws_f),
-                lbs_ws_bwd=_C.ptr(ws_b), posedirs_packed=_C.ptr(core._packed_posedirs()), posedirs_bwd_packed=_C.ptr(core._packed_posedirs_bwd()),
+                **net.fields(), **body_fields,
                 v_template=_C.ptr(core.v_template), shapedirs=_C.ptr(core.shapedirs), j_template=_C.ptr(core.j_template), jdirs=_C.ptr(core.jdirs),
-                skin_idx=_C.ptr(core.skin_idx), skin_w=_C.ptr(core.skin_w), skin_k=int(core.skin_idx.shape[1]), joint_ptr=_C.ptr(jptr),
-                joint_vidx=_C.ptr(jvidx), joint_w=_C.ptr(jw), extra_vertex_ids=_C.ptr(core.extra_vertex_ids), fold=C.pointer(fold[0]),
-                segment_joints_host=segj, num_segments=len(names), orient_segment=names.index("global_orient"), body_segment=names.index("body_pose"),
-                num_vertices=core.V, num_joints=core.J, joint_rows=rows, num_shape=L, num_betas=nb, batch=Bg, row0=g0, inv_batch=1.0 / B,
+                fold=C.pointer(fold[0]), orient_segment=tables.segment("global_orient"), num_shape=L, num_betas=nb, batch=Bg, row0=g0, inv_batch=1.0 / B,
                 n_keypoints=int(kp.shape[1]), joint_map=_C.ptr(jmap_d), map_ptr=_C.ptr(ptr_d), map_entry=_C.ptr(ent_d),
                 op_joints=(C.c_int32 * 4)(*op), gt_joints=(C.c_int32 * 4)(*gt), ign_joints=(C.c_int32 * 8)(*ign), n_ign=len(self.ign_joints),
                 keypoints=_C.ptr(grp[4]), focal_length=_C.ptr(focal_g), camera_center=_C.ptr(center_g),
                 cam_t_est=_C.ptr(est_g), global_orient=_C.ptr(grp[0]), body_pose=_C.ptr(grp[1]), shape=_C.ptr(grp[2]),
                 cam_t=_C.ptr(grp[3]), norm_mode=mode, norm_a=_C.ptr(na), norm_b=_C.ptr(nbv), rot6d=1 if rot6d else 0, num_iters=self.num_iters,
-                n_stages=self.stages, t_host=fa(t_list), w_pose_host=fa(wts["pose_prior_weight"]), w_shape_host=fa(wts["shape_prior_weight"]),
-                w_angle_host=fa(wts["angle_prior_weight"]), sigma=100.0, depth_weight=100.0, lr=float(self.step_size), beta1=0.9, beta2=0.999,
+                n_stages=self.stages, t_host=float_array(t_list), w_pose_host=float_array(wts["pose_prior_weight"]), w_shape_host=float_array(wts["shape_prior_weight"]),
+                w_angle_host=float_array(wts["angle_prior_weight"]), sigma=100.0, depth_weight=100.0, lr=float(self.step_size), beta1=0.9, beta2=0.999,
                 eps=1e-8, seed=seed_v, step0=int(step0) & 0xFFFFFFFF, noise=_C.ptr(nzs), scratch=_C.ptr(scratch), loss_log=_C.ptr(log),
                 reprojection=_C.ptr(grp[5]))
             _C.check(lib.dposer_smplify_optimize(C.byref(a), _C.stream_ptr()), "dposer_smplify_optimize")
