@@ -44,6 +44,11 @@ class PcDesc(C.Structure):
                 ("snr", C.c_float), ("inv_global_batch", C.c_double)]
 
 
+class DpmDesc(C.Structure):
+    """dposer_dpm_desc: order and lower_order_final of dposer_dpm_sampler."""
+    _fields_ = [("order", C.c_int32), ("lower_order_final", C.c_int32)]
+
+
 class BodyDesc(C.Structure):
     _fields_ = [("num_joints", C.c_int32), ("num_vertices", C.c_int32), ("num_shape", C.c_int32),
                 ("num_extra", C.c_int32), ("num_landmarks", C.c_int32)]
@@ -213,6 +218,9 @@ SIGNATURES = {
                                           vp, vp, i64, vp]),
     "dposer_pc_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), C.POINTER(PcDesc), vp, vp, vp, i32, i32, vp, vp, vp, u64, vp, i32,
                                     vp, vp, vp, vp, i64, vp]),
+    "dposer_dpm_coefficients": (C.c_int, [C.POINTER(SdeDesc), C.POINTER(f64), i32, i32, i32, C.POINTER(f64)]),
+    "dposer_dpm_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), C.POINTER(DpmDesc), vp, vp, vp, vp, i32, vp, vp, vp, u64, vp, i32,
+                                     vp, vp, i64, vp]),
     "dposer_guided_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, i32, i32, vp, vp, vp, u64, vp, i32, i32, f32, vp,
                                         vp, vp, i64, vp]),
     "dposer_langevin_step": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, f32, f32, f32, vp, u64, u32, vp, i32, f64, vp, vp,

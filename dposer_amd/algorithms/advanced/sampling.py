@@ -23,6 +23,11 @@ a corrector, other models or SDEs: the generic loop below on top of the HIP scor
 The MCG and DPS completion samplers (``get_guided_sampler``: the loop over ``update_fn_guide``, sampling.py:191-207) run as
 ``dposer_guided_sampler``: per step one network evaluation that keeps its activations, the batch-wide residual norm as a fixed-order sum of
 block partials, one dgrad-only backward and one update kernel; other models / SDEs step ``update_fn_guide`` in Python.
+
+The few-step sampler (``get_dpm_sampler``, ``config.sampling.method = "dpm"``; no counterpart in the reference beyond the first-order step of
+``multi_step_denoise``): DPM-Solver++ (multistep, data prediction) of order 1 or 2 on ``dpm_time_grid`` runs as ``dposer_dpm_sampler`` -- per
+step one network evaluation and one update kernel that combines the state with the last two data predictions under three coefficients
+from the host's float64 schedule (``dposer_dpm_coefficients``).  A ScoreModelFC under continuous sub-VP / VP / VE; anything else raises.
 """
 import abc
 import ctypes as C
@@ -75,6 +80,11 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps, device=None):
     if name == "ode":
         return get_ode_sampler(sde=sde, shape=shape, inverse_scaler=inverse_scaler, denoise=config.sampling.noise_removal, eps=eps,
                                device=device)
+    if name == "dpm":                      # the few-step solver; the config files carry none of its keys
+        return get_dpm_sampler(sde=sde, shape=shape, inverse_scaler=inverse_scaler, steps=int(getattr(config.sampling, "dpm_steps", 20)),
+                               order=int(getattr(config.sampling, "dpm_order", 2)),
+                               skip_type=getattr(config.sampling, "dpm_skip_type", "logSNR"), continuous=config.training.continuous,
+                               denoise=config.sampling.noise_removal, eps=eps, device=device)
     if name != "pc":
         raise ValueError(f"Sampler name {config.sampling.method} unknown.")
     return get_pc_sampler(sde=sde, shape=shape, predictor=get_predictor(config.sampling.predictor.lower()),
@@ -511,6 +521,154 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
             return trajs, (x_mean if denoise else x)
 
     return pc_sampler
+
+
+DPM_SKIP_TYPES = ("logSNR", "time_uniform", "time_quadratic")
+
+
+def _dpm_log_snr(sde, t):
+    """lambda(t) = log(alpha_t / sigma_t) in float64, (alpha, sigma) = return_alpha_sigma (sub-VP: sigma = 1 - exp(2 lmc))."""
+    t = np.asarray(t, dtype=np.float64)
+    if isinstance(sde, sde_lib.VESDE):
+        return -(np.log(sde.sigma_min) + t * np.log(sde.sigma_max / sde.sigma_min))
+    lmc = -0.25 * t ** 2 * (sde.beta_1 - sde.beta_0) - 0.5 * t * sde.beta_0
+    v = -np.expm1(2.0 * lmc)
+    return lmc - np.log(v if isinstance(sde, sde_lib.subVPSDE) else np.sqrt(v))
+
+
+def _dpm_time_of_log_snr(sde, lam):
+    """The inverse of ``_dpm_log_snr`` in closed form."""
+    lam = np.asarray(lam, dtype=np.float64)
+    if isinstance(sde, sde_lib.VESDE):
+        return (-lam - np.log(sde.sigma_min)) / np.log(sde.sigma_max / sde.sigma_min)
+    if isinstance(sde, sde_lib.subVPSDE):      # e^lambda = alpha / (1 - alpha^2)
+        lmc = np.log(2.0) + lam - np.log1p(np.sqrt(1.0 + 4.0 * np.exp(2.0 * lam)))
+    else:                                      # VP: alpha^2 + sigma^2 = 1
+        lmc = -0.5 * np.logaddexp(0.0, -2.0 * lam)
+    b0, db = float(sde.beta_0), float(sde.beta_1 - sde.beta_0)
+    L = -lmc                                   # 1/4 db t^2 + 1/2 b0 t = L, the root that stays finite as db -> 0
+    return 2.0 * L / (0.5 * b0 + np.sqrt(0.25 * b0 * b0 + db * L))
+
+
+def dpm_time_grid(sde, steps, skip_type="logSNR", eps=1e-3, T=None):
+    """The ``steps + 1`` times s_0 = T > ... > s_steps = eps of the few-step solver, float64.  ``"logSNR"``: uniform in
+    lambda = log(alpha / sigma) (what makes 10-30 steps work); ``"time_uniform"``; ``"time_quadratic"``: uniform in sqrt(t).
+    The end points are exactly ``T`` (default ``sde.T``) and ``eps``."""
+    if isinstance(sde, sde_lib._ReverseSDE):
+        sde = sde._fwd
+    if not isinstance(sde, (sde_lib.subVPSDE, sde_lib.VPSDE, sde_lib.VESDE)):
+        raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
+    steps, T, eps = int(steps), float(sde.T if T is None else T), float(eps)
+    if steps < 1 or not 0.0 < eps < T:
+        raise ValueError(f"dpm_time_grid: steps {steps} must be >= 1 and 0 < eps {eps} < T {T}")
+    if skip_type == "logSNR":
+        lam = np.linspace(_dpm_log_snr(sde, T), _dpm_log_snr(sde, eps), steps + 1)
+        ts = _dpm_time_of_log_snr(sde, lam)
+    elif skip_type == "time_uniform":
+        ts = np.linspace(T, eps, steps + 1)
+    elif skip_type == "time_quadratic":
+        ts = np.linspace(np.sqrt(T), np.sqrt(eps), steps + 1) ** 2
+    else:
+        raise ValueError(f"unknown skip_type {skip_type!r}: expected one of {DPM_SKIP_TYPES}")
+    ts = np.array(ts, dtype=np.float64)
+    ts[0], ts[-1] = T, eps
+    return ts
+
+
+def dpm_coefficients(sde, times, order, lower_order_final=True, continuous=True):
+    """dposer_dpm_coefficients: the (c_x, c_0, c_1) of every step x <- c_x x + c_0 D_i + c_1 D_{i-1} on the grid ``times`` (n + 1 decreasing
+    times), float64 [n, 3].  Host only: no GPU is needed."""
+    desc = sde_lib.sde_desc(sde, continuous)
+    if desc is None:
+        raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
+    times = np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
+    n = times.shape[0] - 1
+    out = np.zeros((max(n, 1), 3), dtype=np.float64)
+    _C.check(_C.lib().dposer_dpm_coefficients(C.byref(desc), times.ctypes.data_as(C.POINTER(C.c_double)), int(n), int(order),
+                                              int(bool(lower_order_final)), out.ctypes.data_as(C.POINTER(C.c_double))), "dposer_dpm_coefficients")
+    return out[:n]
+
+
+def fused_dpm_supported(sde, model, continuous=True):
+    """What ``dposer_dpm_sampler`` takes: a ScoreModelFC under the continuous sub-VP / VP / VE score function."""
+    from .model import ScoreModelFC
+    return bool(continuous) and isinstance(model, ScoreModelFC) and sde_lib.sde_desc(sde, True) is not None
+
+
+def fused_dpm_sample(model, sde, x, times, *, order=2, lower_order_final=True, observation=None, mask=None, noise=None, seed=0,
+                     traj_stride=0, continuous=True):
+    """dposer_dpm_sampler: the ``len(times) - 1`` solver steps in ONE library call.  x [B, D] the state at times[0] (not modified); returns
+    (trajs or None, x at times[-1], x0_hat = the last data prediction).  ``noise`` [n, B, D]: injected imputation draws (completion)."""
+    from .model import ScoreModelFC
+    if not isinstance(model, ScoreModelFC) or sde_lib.sde_desc(sde, continuous) is None:
+        raise NotImplementedError("the DPM-Solver++ sampler runs a ScoreModelFC under sub-VP / VP / VE as one HIP call; there is no other path")
+    times = torch.as_tensor(np.asarray(times, dtype=np.float64)).reshape(-1)
+    n = int(times.shape[0]) - 1
+    # the host entry's argument checks (grid, order, SDE kind) on the fp32 times the call will see, before any GPU work
+    dpm_coefficients(sde, times.float().double().numpy(), order, lower_order_final, continuous)
+    p = _fused_prelude(model, sde, x, times, max(n, 0), traj_stride, continuous, observation, mask, noise)
+    x0_hat = torch.empty_like(p.x)
+    if p.B == 0:
+        return p.traj, p.x, x0_hat
+    eng, B = p.eng, p.B
+    hist = torch.empty_like(p.x)
+    ws = eng.workspace(B, _C.WS_SHARED_T, max(n, 1), x.device)
+    dpm = _C.DpmDesc(int(order), int(bool(lower_order_final)))
+    _C.check(eng.lib.dposer_dpm_sampler(eng.h, _C.ptr(p.flat), _C.ptr(p.packed), _C.ptr(ws), C.byref(p.desc), C.byref(dpm), _C.ptr(p.x),
+                                        _C.ptr(x0_hat), _C.ptr(hist), C.c_void_p(p.ts_host.data_ptr()), n, _C.ptr(p.obs), _C.ptr(p.msk),
+                                        _C.ptr(p.nz), int(seed), _C.ptr(p.traj), int(traj_stride or 1),
+                                        _C.ptr(eng.freq(x.device, model._fourier_W())), _C.ptr(model.sigmas), B, _C.stream_ptr()),
+             "dposer_dpm_sampler")
+    return p.traj, p.x, x0_hat
+
+
+def get_dpm_sampler(sde, shape, inverse_scaler, steps=20, order=2, skip_type="logSNR", lower_order_final=True, continuous=True,
+                    denoise=False, eps=1e-3, device="cuda"):
+    """The few-step sampler: DPM-Solver++ (multistep, data prediction) of order 1 (= DDIM) or 2 on ``dpm_time_grid(sde, steps, skip_type,
+    eps)``, ``steps`` network evaluations per sample in one library call (``fused_dpm_sample``).
+
+    ``dpm_sampler(model, observation=None, mask=None, z=None, args=None, noise=None, seed=None, traj_stride=1)`` returns
+    ``(trajs [steps // traj_stride, B, D], samples)`` shaped as ``pc_sampler`` returns them; ``denoise=True`` returns the last data
+    prediction x0_hat in place of the state at ``eps``.  With ``observation`` and ``mask`` it completes: the state is imputed at every
+    grid time before the network sees it, and the samples carry the observation on the mask.  A model or SDE the call does not
+    take raises: there is no step-by-step path."""
+    if isinstance(sde, sde_lib._ReverseSDE):
+        sde = sde._fwd
+    times = dpm_time_grid(sde, steps, skip_type, eps)
+    call_count = [0]
+
+    def dpm_sampler(model, observation=None, mask=None, z=None, args=None, noise=None, seed=None, traj_stride=1):
+        if (observation is None) != (mask is None):
+            raise ValueError("observation and mask go together")
+        completion = observation is not None and (args is None or getattr(args, "task", "completion") in ["completion"])
+        if z is not None and tuple(z.shape) != tuple(shape):
+            raise ValueError(f"z {tuple(z.shape)} does not have the sampler's shape {tuple(shape)}")
+        if completion and (tuple(observation.shape) != tuple(shape) or tuple(mask.shape) != tuple(shape)):
+            raise ValueError(f"observation {tuple(observation.shape)} / mask {tuple(mask.shape)} do not have the sampler's shape {tuple(shape)}")
+        if noise is not None and tuple(noise.shape) != (int(steps),) + tuple(shape):
+            raise ValueError(f"noise {tuple(noise.shape)}: expected {(int(steps),) + tuple(shape)}")
+        x = sde.prior_sampling(shape).to(device) if z is None else z
+        call_count[0] += 1
+        if seed is None:
+            seed = (getattr(model, "_rng_seed", 0) * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                trajs, x, x0_hat = fused_dpm_sample(model, sde, x, times, order=order, lower_order_final=lower_order_final,
+                                                    observation=observation if completion else None, mask=mask if completion else None,
+                                                    noise=noise if completion else None, seed=seed, traj_stride=traj_stride,
+                                                    continuous=continuous)
+        finally:
+            model.train(was_training)
+        if trajs is None:
+            trajs = x.new_empty((0,) + tuple(x.shape))
+        out = x0_hat if denoise else x
+        if completion:
+            out = observation * mask + out * (1 - mask)
+        return trajs, out
+
+    return dpm_sampler
 
 
 GUIDED_METHODS = ("dps", "mcg")

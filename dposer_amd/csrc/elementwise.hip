@@ -530,6 +530,56 @@ hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st)
     return hipGetLastError();
 }
 
+// One DPM-Solver++ (2M, data prediction) step behind the network evaluation at s_i (include/dposer_hip.h: dposer_dpm_sampler):
+//   D_i = (x + sigma_s^2 score) / alpha_s   (k_denoise's data prediction);   x <- cx x + c0 D_i + c1 D_{i-1}
+// with the three coefficients by value -- the exponential-integrator schedule is the host's, in float64; nothing here takes a log or a
+// difference of log-SNRs.  D_i replaces D_{i-1} in `hist` (read only at effective order 2) and is the last step's x0_hat.  A completion
+// imputes the new state at s_{i+1} in the same pass (the draw of k_em_update's look-ahead: STREAM_IMPUTE_A at step + 1).  The state leaves
+// as fp32 rows and FT-tiled for the next GEMM (padded rows / columns zero, as k_perturb_shared writes them).  Each thread owns its
+// elements of x / hist / x0_hat / traj, so the in-place updates need no ordering.
+template <typename T> __global__ void __launch_bounds__(256) k_dpm_update(WithSde<DpmUpdateArgs> d) {
+    const DpmUpdateArgs& a = d.a;
+    const int qx = a.Dpad >> 2;
+    const int QD = (a.D + 3) >> 2;
+    const int64_t total = a.Bpad * qx;
+    const SdeAt at = sde_at(d.sde, a.t);
+    const float alpha = at.mc, sigma2 = at.sd * at.sd;                   // return_alpha_sigma at s_i, sde_lib.py:177-181 / :227-231 / :289-292
+    const float usig = launch_usig(a, at.label);
+    const bool ahead = a.obs && a.t_next >= 0.f;
+    float mcn = 0.f, sdn = 0.f;
+    if (ahead) { const SdeAt an = sde_at(d.sde, a.t_next); mcn = an.mc; sdn = an.sd; }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qx;
+        const int q = (int)(i % qx);
+        const int c = q * 4;
+        f32x4 xn = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+            const f32x4 r4 = *reinterpret_cast<const f32x4*>(a.res + s * a.Cp + c);
+            float za[4];
+            if (ahead && !a.z_imp) normals4((uint64_t)s * QD + q, STREAM_IMPUTE_A, a.step + 1, a.seed, za);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const int64_t o = s * a.D + c + r;
+                const float x0 = a.x[o];
+                const float model = r4[r] / usig;
+                const float score = sde_score(d.sde, model, at.sd_score);     // utils.py:155,162 / :180
+                const float Di = (x0 + sigma2 * score) / alpha;               // completion.py:107
+                float x = a.cx * x0 + a.c0 * Di;
+                if (a.use_hist) x = x + a.c1 * a.hist[o];
+                if (a.hist) a.hist[o] = Di;
+                if (a.x0_hat) a.x0_hat[o] = Di;
+                if (a.traj) a.traj[o] = x;
+                if (ahead) x = impute(x, a.mask[o], a.obs[o], mcn, a.z_imp ? a.z_imp[o] : za[r], sdn);   // sampling.py:416-420 at s_{i+1}
+                a.x[o] = x;
+                xn[r] = x;
+            }
+        }
+        store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
+    }
+}
+hipError_t launch_dpm_update(const DpmUpdateArgs& a, hipStream_t st) { return launch_quads(k_dpm_update<float>, k_dpm_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
+
 // MotionDenoise.RED_Diff (run/motion_denoising.py:145-154) behind the network evaluation at x_t = mean + std z:
 //   eps_pred = -score * std;   weight = sqrt(sigma^2) / alpha;   guidance = mean_b(weight * <(eps_pred - z).detach(), x_0>)
 // and its gradient weight (eps_pred - z) / B w.r.t. x_0.  z is the perturbation's: the injected array, or the Philox draws of

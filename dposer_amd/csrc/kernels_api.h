@@ -168,6 +168,20 @@ struct DdimStepArgs {      // one step of multi_step_denoise behind its network 
 };
 hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st);
 
+struct DpmUpdateArgs : UpdateCommon {   // one DPM-Solver++ (multistep, data prediction) step behind its network evaluation at t = s_i (dposer_dpm_sampler)
+    // x: read and written as [B][D] rows; x_mean: unused (null)
+    float* hist;           // [B][D] data prediction of the previous step: read when use_hist, always overwritten with this step's (null: neither)
+    float* x0_hat;         // last step: [B][D] this step's data prediction, else null
+    const float* obs;      // completion: observation [B][D] or null
+    const float* mask;     // completion: mask [B][D]
+    float* traj;           // [B][D] slot of this step (the state before the look-ahead imputation) or null
+    const float* z_imp;    // injected draw of the imputation at t_next, or null (-> Philox STREAM_IMPUTE_A at step + 1)
+    float t_next;          // s_{i+1} when the state is imputed there (completion, not the last step); < 0: no imputation
+    float cx, c0, c1;      // x <- cx x + c0 D_i + c1 D_{i-1}: the host's float64 schedule rounded once (dposer_dpm_coefficients)
+    int use_hist;          // effective order 2: c1 D_{i-1} is read and added
+};
+hipError_t launch_dpm_update(const DpmUpdateArgs& a, hipStream_t st);
+
 struct RedDiffArgs {       // MotionDenoise.RED_Diff behind its network evaluation (run/motion_denoising.py:145-154)
     const float* res;      // [Bpad][Cp] model output at x_t
     const float* x0;       // [B][D]

@@ -1061,6 +1061,118 @@ extern "C" int dposer_em_sampler_steps(dposer_scorefc_t h, const float* flat, co
                    traj_stride, freq, sigmas, B, stream);
 }
 
+// ---- DPM-Solver++ (multistep, data prediction), orders 1 and 2: include/dposer_hip.h has the rule ---------------------------------------
+// (alpha, sigma) of return_alpha_sigma in float64, in the reference's operation order (sde_lib.py:177-181, :227-231, :289-292; sub-VP:
+// sigma = 1 - exp(2 lmc)), from the descriptor's doubles
+static void dpm_alpha_sigma(const dposer_sde_desc* s, double t, double* alpha, double* sigma) {
+    if (s->kind == DPOSER_SDE_VE) {
+        *alpha = 1.0;
+        *sigma = s->beta_min * pow(s->beta_max / s->beta_min, t);
+        return;
+    }
+    const double lmc = (-0.25 * (t * t)) * (s->beta_max - s->beta_min) - (0.5 * t) * s->beta_min;
+    const double v = 1.0 - exp(2.0 * lmc);
+    *alpha = exp(lmc);
+    *sigma = s->kind == DPOSER_SDE_SUBVP ? v : sqrt(v);
+}
+// min(order, i + 1), and with lower_order_final also min(., n - i): the start-up step and the last step run at order 1
+static inline int dpm_effective_order(int order, int lower_order_final, int i, int n) {
+    int eff = order < i + 1 ? order : i + 1;
+    if (lower_order_final && eff > n - i) eff = n - i;
+    return eff;
+}
+// argument checks + schedule of both DPM entries; `t_of(i)` reads the caller's grid (doubles, or the sampler's fp32 times widened)
+template <typename TimeAt>
+static int dpm_schedule(const char* entry, const dposer_sde_desc* sde, TimeAt t_of, int32_t n, int32_t order, int32_t lower_order_final, double* coef) {
+    const std::string who = std::string(entry) + ": ";
+    if (!sde) return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "null argument");
+    if (!sde_kind_ok(sde)) return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "unknown SDE kind");
+    if (!sde_kind_continuous(sde))
+        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, who + "continuous score functions only (sub-VP, VP, VE): the solver integrates the continuous-time "
+                                                              "marginals, the discrete kinds have no log-SNR schedule here");
+    if (order != 1 && order != 2) return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "order must be 1 or 2");
+    if (n < 1) return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "n_steps must be >= 1");
+    if (sde->kind == DPOSER_SDE_VE ? !(sde->beta_min > 0.0 && sde->beta_max > sde->beta_min) : !(sde->beta_min >= 0.0 && sde->beta_max >= sde->beta_min && sde->beta_max > 0.0))
+        return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "bad SDE constants");
+    for (int i = 0; i <= n; ++i) {
+        const double t = t_of(i);
+        if (!(t > 0.0 && t <= sde->T) || (i > 0 && !(t < t_of(i - 1))))
+            return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "times must be strictly decreasing and inside (0, T]");
+    }
+    std::vector<double> lam(n + 1), al(n + 1), sg(n + 1);
+    for (int i = 0; i <= n; ++i) {
+        dpm_alpha_sigma(sde, t_of(i), &al[i], &sg[i]);
+        if (!(sg[i] > 0.0 && al[i] > 0.0)) return dposer_set_error(DPOSER_ERR_BAD_ARG, who + "sigma(t) underflows at a grid time");
+        lam[i] = log(al[i] / sg[i]);
+    }
+    for (int i = 0; i < n; ++i) {
+        const int eff = dpm_effective_order(order, lower_order_final, i, n);
+        const double h = lam[i + 1] - lam[i];
+        const double e = -al[i + 1] * expm1(-h);
+        coef[3 * i + 0] = sg[i + 1] / sg[i];
+        coef[3 * i + 1] = e;
+        coef[3 * i + 2] = 0.0;
+        if (eff == 2) {
+            const double r = (lam[i] - lam[i - 1]) / h;
+            coef[3 * i + 1] = e + 0.5 * e / r;
+            coef[3 * i + 2] = -0.5 * e / r;
+        }
+    }
+    return DPOSER_OK;
+}
+extern "C" int dposer_dpm_coefficients(const dposer_sde_desc* sde, const double* times_host, int32_t n_steps, int32_t order,
+                                       int32_t lower_order_final, double* coef_out) {
+    DP_CHECK_ARG(times_host && coef_out, "null argument");
+    return dpm_schedule(__func__, sde, [&](int i) { return times_host[i]; }, n_steps, order, lower_order_final, coef_out);
+}
+
+// The few-step sampler: every step is one network evaluation on its time-table row + k_dpm_update, which leaves the new state (imputed at
+// the next time under a completion) FT-tiled in w.xin.  Host loop in pc_loop's manner; the schedule is formed before anything is launched.
+extern "C" int dposer_dpm_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                                  const dposer_dpm_desc* dpm, float* x, float* x0_hat, float* hist, const float* times_host, int32_t n_steps,
+                                  const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
+                                  int32_t traj_stride, const float* freq, const float* sigmas, int64_t B, void* stream) {
+    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    DP_CHECK_ARG(sde && dpm && x && times_host && freq && sigmas, "null argument");
+    DP_CHECK_ARG((observation == nullptr) == (mask == nullptr), "observation and mask go together");
+    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
+    DP_CHECK_ARG(dpm->order != 2 || hist, "hist is required at order 2");
+    std::vector<double> coef(3 * (size_t)(n_steps > 0 ? n_steps : 1));
+    DP_TRY(dpm_schedule(__func__, sde, [&](int i) { return (double)times_host[i]; }, n_steps, dpm->order, dpm->lower_order_final, coef.data()));
+    DP_RANGE();                                      // (every argument check is above: a refused call opens no range and launches nothing)
+    g_alg_batch = B;
+    hipStream_t st = (hipStream_t)stream;
+    const char* packed = (const char*)packed_;
+    Ws w;
+    layout_ws(h, B, DPOSER_WS_SHARED_T, n_steps, (char*)ws_, w);
+    DP_TRY(stage_step_labels(h, w, sde, times_host, n_steps, st));      // the network is evaluated at s_0 .. s_{n-1}
+    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_steps, freq, st));
+    const int64_t BD = B * h->D;
+    const UpdateCommon uc = update_common(h, w, sde, sigmas, x, nullptr, seed, B);
+    {   // imputation at s_0 (completion) + pack x: k_em_update's stand-alone form, its draw STREAM_IMPUTE_A keyed at 0
+        EmUpdateArgs ea{};
+        static_cast<UpdateCommon&>(ea) = uc; ea.obs = observation; ea.mask = mask;
+        ea.res = nullptr; ea.t = times_host[0]; ea.t_next = times_host[0]; ea.step = (uint32_t)-1;
+        ea.z_impA = (noise && observation) ? noise : nullptr;
+        DP_CHECK_HIP(launch_em_update(ea, st));
+    }
+    DpmUpdateArgs da{};
+    static_cast<UpdateCommon&>(da) = uc; da.obs = observation; da.mask = mask; da.hist = hist;
+    for (int i = 0; i < n_steps; ++i) {
+        DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+        const bool last = i + 1 == n_steps;
+        const bool ahead = observation && !last;
+        da.t = times_host[i]; da.t_next = ahead ? times_host[i + 1] : -1.0f; da.step = (uint32_t)i;
+        da.cx = (float)coef[3 * i]; da.c0 = (float)coef[3 * i + 1]; da.c1 = (float)coef[3 * i + 2];
+        da.use_hist = dpm_effective_order(dpm->order, dpm->lower_order_final, i, n_steps) == 2;
+        da.z_imp = (noise && ahead) ? noise + (int64_t)(i + 1) * BD : nullptr;
+        da.x0_hat = last ? x0_hat : nullptr;
+        da.traj = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
+        DP_CHECK_HIP(launch_dpm_update(da, st));
+    }
+    return DPOSER_OK;
+}
+
 // LangevinCorrector.update_fn (sampling.py:282-302), one corrector step at a shared t, in two phases around the batch means:
 //   phase 0: pack x, evaluate the network, write sum_b ||grad_b|| and sum_b ||noise_b|| of THIS rank's samples to norm_sums[0..1]
 //   (the caller all-reduces the two floats over the data-parallel ranks -- or not, on one GPU)

@@ -106,7 +106,7 @@ class DPoserComp:
         return observation * mask + x.detach() * (1.0 - mask)
 
 
-SOLVERS = ("dposer", "scoresde", "mcg", "dps")
+SOLVERS = ("dposer", "scoresde", "mcg", "dps", "dpm")
 
 
 class _TaskArgs:
@@ -130,6 +130,17 @@ def _completion_solver(solver, model, sde, continuous, shape, device, solver_kwa
                                      continuous=continuous, denoise=kw.pop("denoise", True), eps=eps, device=device, **kw)
         args = _TaskArgs("completion")
         return lambda observation, mask: fn(model, observation=observation, mask=mask, args=args, **extra)[1]
+    if solver == "dpm":                              # the few-step solver: `steps` network evaluations per hypothesis
+        fn = sampling.get_dpm_sampler(sde, shape, lambda v: v, steps=kw.pop("steps", 20), order=kw.pop("order", 2),
+                                      skip_type=kw.pop("skip_type", "logSNR"), continuous=continuous, denoise=kw.pop("denoise", True), eps=eps,
+                                      device=device, **kw)
+        seed0, calls = extra.pop("seed", None), [0]
+
+        def complete(observation, mask):             # a given seed keys the first call; every further call (hypothesis, batch) the next one
+            calls[0] += 1
+            return fn(model, observation=observation, mask=mask, seed=None if seed0 is None else int(seed0) + calls[0] - 1, **extra)[1]
+
+        return complete
     fn = sampling.get_guided_sampler(sde, shape, lambda v: v, solver, continuous=continuous, eps=eps, device=device, **kw)
     return lambda observation, mask: fn(model, observation, mask, **extra)[1]
 
@@ -145,7 +156,8 @@ def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs
     of (sum, count) pairs (``distributed.reduce_metric_means``) instead of ``gather_object`` of every value (:300-305).
     ``poses`` [N, D] normalised test poses (the dataset's ``poses`` tensor); returns ``({metric: mean}, samples evaluated here)``.
     ``solver``: "dposer" (the optimisation above, ``optimize_kwargs``) or one of the diffusion samplers "scoresde" | "mcg" | "dps"
-    (``solver_kwargs``: ``grad_step`` for MCG / DPS, ``eps``, ``denoise``, ``seed``); each hypothesis is one sampler call.
+    (``solver_kwargs``: ``grad_step`` for MCG / DPS, ``eps``, ``denoise``, ``seed``) or the few-step "dpm" (DPM-Solver++:
+    ``steps``, ``order``, ``skip_type``, ``eps``, ``seed``); each hypothesis is one sampler call, for "dpm" with its own seed.
     ``fused_eval``: score with ``Evaler.multi_eval_bodys(fused=True)`` -- one ``dposer_pose_pair_errors`` call per batch, no vertex tensors."""
     if solver not in SOLVERS:
         raise ValueError(f"unknown completion solver {solver!r}: expected one of {SOLVERS}")

@@ -22,15 +22,17 @@ FPS = 30
 
 def generation_process(model, sde, config, normalizer, body_model, target_path, video_num=3, *, sampling_eps=1e-3, inverse_scaler=None,
                        pose_dim=None, device=None, seed=None, name="generation_process{}.mp4"):
-    """demo.py:164-209.  ``config.sampling.method`` must be 'pc' (the ODE sampler keeps no trajectory).  Writes ``video_num`` videos of
-    ``sde.N // 10`` frames into ``target_path`` and returns their paths."""
+    """demo.py:164-209.  ``config.sampling.method`` must be 'pc' or 'dpm' (the ODE sampler keeps no trajectory).  Writes ``video_num``
+    videos of ``sde.N // 10`` frames ('dpm': one frame per solver step) into ``target_path`` and returns their paths."""
     os.makedirs(target_path, exist_ok=True)
-    assert config.sampling.method == "pc"               # we don't save trajectories for ode sampler
+    method = str(config.sampling.method).lower()
+    assert method in ("pc", "dpm")                      # we don't save trajectories for ode sampler
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     D = int(pose_dim) if pose_dim is not None else int(model.n_poses * model.joint_dim)
     fn = sampling.get_sampling_fn(config, sde, (video_num, D), inverse_scaler or (lambda v: v), sampling_eps, device=dev)
     kw = {} if seed is None else {"seed": seed}
-    trajs, _ = fn(model, observation=None, traj_stride=STRIDE, **kw)            # [N // 10, video_num, D] == trajs[9::10]
+    # 'pc': [N // 10, video_num, D] == trajs[9::10];  'dpm': the few-step solver has config.sampling.dpm_steps states, all kept
+    trajs, _ = fn(model, observation=None, traj_stride=STRIDE if method == "pc" else 1, **kw)
     num_frame = int(trajs.shape[0])
     with torch.no_grad():
         poses = normalizer.offline_denormalize(trajs.transpose(0, 1).reshape(video_num * num_frame, D), to_axis=True)

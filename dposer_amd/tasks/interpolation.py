@@ -30,10 +30,20 @@ def encode(model, sde, x, *, rtol=1e-4, atol=1e-4, eps=1e-4, epsilon=None):
     return z
 
 
-def decode(model, sde, z, eps=1e-5, *, continuous=True, seed=None):
+DECODERS = ("pf", "dpm")
+
+
+def decode(model, sde, z, eps=1e-5, *, continuous=True, seed=None, decoder="pf", decoder_kw=None):
     """Latents z [n, D] -> poses [n, D]: the probability-flow pc_sampler from z (demo.py:437-450), no trajectory kept.  Deterministic:
-    the result does not depend on ``seed`` (it keys no draw on this path)."""
+    the result does not depend on ``seed`` (it keys no draw on this path).  ``decoder="dpm"``: the same ODE solved by the few-step
+    DPM-Solver++ sampler (``decoder_kw``: ``steps``, ``order``, ``skip_type``), also deterministic."""
+    if decoder not in DECODERS:
+        raise ValueError(f"unknown decoder {decoder!r}: expected one of {DECODERS}")
     z = z.reshape(-1, z.shape[-1])
+    if decoder == "dpm":
+        fn = sampling.get_dpm_sampler(sde, tuple(z.shape), lambda v: v, continuous=continuous, denoise=False, eps=eps, device=z.device,
+                                      **(decoder_kw or {}))
+        return fn(model, z=z.contiguous(), traj_stride=0, seed=seed)[1]
     fn = sampling.get_pc_sampler(sde, tuple(z.shape), sampling.EulerMaruyamaPredictor, sampling.NoneCorrector, lambda v: v, snr=0.16,
                                  n_steps=1, probability_flow=True, continuous=continuous, denoise=True, eps=eps, device=z.device)
     _, x = fn(model, z=z.contiguous(), traj_stride=0, seed=seed)
@@ -47,12 +57,14 @@ def slerp_segments(z, frames):
     return torch.stack([slerp_interpolation(z[s], z[s + 1], frames) for s in range(z.shape[0] - 1)])
 
 
-def interpolate(model, sde, anchors, frames=60, eps=1e-5, *, continuous=True, encode_kw=None):
+def interpolate(model, sde, anchors, frames=60, eps=1e-5, *, continuous=True, encode_kw=None, decoder="pf", decoder_kw=None):
     """demo.py:412-504 without rendering: anchors [n, D] -> (anchor_z [n, D], reconstructions [n, D], frames [n - 1, frames, D]).
-    The reconstructions decode the anchors' latents; the frames decode every segment's latents in one sampler call."""
+    The reconstructions decode the anchors' latents; the frames decode every segment's latents in one sampler call.
+    ``decoder``: "pf" (the reference's 1000-step probability-flow sampler) or "dpm" (the few-step solver, ``decoder_kw``)."""
     anchor_z = encode(model, sde, anchors, **(encode_kw or {}))
-    recon = decode(model, sde, anchor_z, eps, continuous=continuous)
+    dec = dict(continuous=continuous, decoder=decoder, decoder_kw=decoder_kw)
+    recon = decode(model, sde, anchor_z, eps, **dec)
     lat = slerp_segments(anchor_z, frames)
     S, D = lat.shape[0], lat.shape[-1]
-    out = decode(model, sde, lat.reshape(S * frames, D), eps, continuous=continuous) if S else lat.clone()
+    out = decode(model, sde, lat.reshape(S * frames, D), eps, **dec) if S else lat.clone()
     return anchor_z, recon, out.reshape(S, frames, D)

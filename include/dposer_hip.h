@@ -398,6 +398,46 @@ int dposer_pc_sampler(dposer_scorefc_t h, const float* flat_params, const void* 
                       int32_t traj_stride, const float* disc_table_host, float* norm_sums, const float* freq, const float* sigmas,
                       int64_t batch, void* stream);
 
+/* DPM-Solver++ (multistep, data prediction; Lu et al. 2022), orders 1 and 2: the few-step sampler.  The reference has no counterpart
+ * beyond its first-order member, one step of multi_step_denoise (run/completion.py:112-129).
+ * For the marginal x_t = alpha_t x_0 + sigma_t z -- (alpha, sigma) = return_alpha_sigma, sde_lib.py:177-181, :227-231, :289-292, so for
+ * sub-VP sigma = 1 - exp(2 lmc) as everywhere in this library -- let lambda_t = log(alpha_t / sigma_t).  Times s_0 > s_1 > ... > s_n, state
+ * x at s_0.  Step i goes from s = s_i to t = s_{i+1}, h = lambda_t - lambda_s:
+ *   D_i = (x + sigma_s^2 score(x, s)) / alpha_s                                    the data prediction (completion.py:105-110)
+ *   order 1:  x <- (sigma_t / sigma_s) x - alpha_t expm1(-h) D_i                    (= DDIM = one step of multi_step_denoise)
+ *   order 2:  x <- (sigma_t / sigma_s) x - alpha_t expm1(-h) D_i - 1/2 alpha_t expm1(-h) (D_i - D_{i-1}) / r,
+ *             r = (lambda_s - lambda_{s_{i-1}}) / h
+ *   effective order at step i = min(order, i + 1), with lower_order_final also min(., n - i).
+ * Every step is  x <- c_x x + c_0 D_i + c_1 D_{i-1}.  dposer_dpm_coefficients forms (c_x, c_0, c_1) in float64 on the HOST: no stream, no
+ * device memory, callable without a GPU.
+ *   times_host [n_steps + 1] HOST doubles, strictly decreasing, inside (0, sde.T];  coef_out [n_steps][3] HOST doubles (c_1 = 0 at
+ *   effective order 1);  order 1 or 2.  DPOSER_SDE_SUBVP / _VP / _VE: the discrete kinds return DPOSER_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t order;              /* 1 or 2 */
+    int32_t lower_order_final;  /* the last step at order 1 (what few-step grids want) */
+} dposer_dpm_desc;
+int dposer_dpm_coefficients(const dposer_sde_desc* sde, const double* times_host, int32_t n_steps, int32_t order,
+                            int32_t lower_order_final, double* coef_out);
+/* The sampler: all n_steps steps are enqueued by one call, nothing synchronises with the host, all memory is the caller's.  Per step one
+ * network evaluation at s_i and one update kernel that reads the coefficients by value (the schedule above at the fp32 times widened
+ * to double, rounded once to fp32).
+ *   x [B, D]             in: the state at s_0, out: the state at s_n;
+ *   x0_hat [B, D]        out or NULL: D_{n-1}, the last data prediction (the "denoised" sample);
+ *   hist [B, D]          scratch for D_{i-1}; never read at a step of effective order 1, so it needs no initialisation; may be NULL at order 1;
+ *   times_host           [n_steps + 1] HOST floats, as above; the network is evaluated at times_host[0 .. n_steps - 1];
+ *   observation / mask   [B, D] or NULL (completion): the state is imputed at s_i before the evaluation at s_i,
+ *                        x <- x (1 - mask) + (alpha_s observation + sigma_s z_i) mask (sampling.py:416-420 at s_i); the state returned after
+ *                        the last update is NOT imputed (the caller blends observation * mask + x * (1 - mask));
+ *   noise [n_steps][B][D] the draws z_i, or NULL -> Philox STREAM_IMPUTE_A keyed at i (the draw dposer_em_sampler makes ahead of its
+ *                        predictor at loop index i); read only with an observation;
+ *   traj [n_steps / traj_stride][B][D] or NULL: the state after step i (before the imputation at s_{i+1}) when (i + 1) % traj_stride == 0.
+ * Every argument is checked before anything is launched; the discrete kinds return DPOSER_ERR_UNSUPPORTED.
+ * Workspace: DPOSER_WS_SHARED_T with n_steps table rows. */
+int dposer_dpm_sampler(dposer_scorefc_t h, const float* flat_params, const void* packed, void* ws, const dposer_sde_desc* sde,
+                       const dposer_dpm_desc* dpm, float* x, float* x0_hat, float* hist, const float* times_host, int32_t n_steps,
+                       const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
+                       const float* freq, const float* sigmas, int64_t batch, void* stream);
+
 /* The MCG / DPS guided samplers for pose completion, one call: the loop of sampling.py:455-461 over
  * EulerMaruyamaPredictor.update_fn_guide (sampling.py:191-207, "this can be used to implement MCG and DPS") around
  * RSDE.sde(guide=True) (sde_lib.py:98-109).  Loop indices [start_step, start_step + n_steps) (n_steps < 0: to N) are enqueued, nothing
