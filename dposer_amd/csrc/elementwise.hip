@@ -306,6 +306,14 @@ template <typename A> static hipError_t launch_quads(void (*k32)(WithSde<A>), vo
 template <typename A> __device__ __forceinline__ float launch_usig(const A& a, float label) {
     return a.scale_by_sigma ? used_sigma(a.sigmas, a.num_scales, label, a.scale_by_sigma == 2) : 1.0f;
 }
+// The per-element chain behind a network evaluation, in the operation order every call site had (this file is built with contraction off):
+// the score from post_dense's output: res / used_sigmas (model.py:194), then -model / std, VE: the model itself (utils.py:155,160,162 / :180)
+__device__ __forceinline__ float score_of_res(const SdeDev& sde, float res, float usig, float sd_score) { return sde_score(sde, res / usig, sd_score); }
+// Tweedie's estimate of x_0 from x_t and the score (completion.py:107, sampling.py:200): alpha, sigma^2 of return_alpha_sigma
+__device__ __forceinline__ float tweedie_x0(float xt, float sigma2, float score, float alpha) { return (xt + sigma2 * score) / alpha; }
+// the SNR loss weight 0.5 sqrt(1 + snr) (completion.py:143).  The one-step losses pass snr = alpha / sqrt(sigma^2) (completion.py:108), the
+// multi-step loss alpha / sigma (completion.py:128): the callers form it, the two are not the same fp32 expression
+__device__ __forceinline__ float snr_loss_weight(float snr) { return 0.5f * sqrtf(1.0f + snr); }
 // completion imputation (sampling.py:416-420): x (1 - mask) + (mean + z std) mask, mean = mc * observation
 __device__ __forceinline__ float impute(float x, float m, float obs, float mc, float z, float sd) { return x * (1.0f - m) + (mc * obs + z * sd) * m; }
 template <typename T> __global__ void __launch_bounds__(256) k_em_update(WithSde<EmUpdateArgs> d) {
@@ -337,8 +345,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_em_update(WithSde
                 float x = a.x[o];
                 if (a.res) {
                     // score = -(res / used_sigmas) / std                         model.py:194, utils.py:162
-                    const float model = a.res[s * a.Cp + c + r] / usig;
-                    const float score = sde_score(d.sde, model, at.sd_score);
+                    const float score = score_of_res(d.sde, a.res[s * a.Cp + c + r], usig, at.sd_score);
                     // rsde.sde: drift = -0.5 beta x - g^2 score (* 0.5 under probability flow)   sde_lib.py:98-104
                     float drift = (-0.5f * beta) * x;
                     drift = drift - ((g * g) * score) * (a.pf ? 0.5f : 1.0f);
@@ -434,22 +441,18 @@ hipError_t launch_perturb_shared(const PerturbSharedArgs& a, hipStream_t st) { r
 
 __global__ void __launch_bounds__(256) k_denoise(WithSde<DenoiseArgs> d) {
     const DenoiseArgs& a = d.a;
-    const float t = a.t;
-    const SdeAt at = sde_at(d.sde, t);
+    const SdeAt at = sde_at(d.sde, a.t);
     const float alpha = at.mc, sigma = at.sd;                         // return_alpha_sigma, sde_lib.py:227-231 (VE: 1, sigma(t), :289-292)
     const float sigma2 = sigma * sigma;
-    const float label = at.label;
-    const float usig = launch_usig(a, label);
-    const float snr = alpha / sqrtf(sigma2);                          // completion.py:108
-    const float w = a.weighted ? 0.5f * sqrtf(1.0f + snr) : 0.5f;     // completion.py:143-146
+    const float usig = launch_usig(a, at.label);
+    const float w = a.weighted ? snr_loss_weight(alpha / sqrtf(sigma2)) : 0.5f;     // completion.py:108,143-146
     float acc = 0.f;
     const int64_t total = a.B * a.D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t s = i / a.D;
         const int c = (int)(i % a.D);
-        const float model = a.res[s * a.Cp + c] / usig;
-        const float score = sde_score(d.sde, model, at.sd_score);     // utils.py:155,162 (std == sigma; the DDPM table's entry for a discrete VP score function, :160)
-        const float x0h = (a.xt[s * a.Dpad + c] + sigma2 * score) / alpha;   // completion.py:107
+        const float score = score_of_res(d.sde, a.res[s * a.Cp + c], usig, at.sd_score);   // (std == sigma; the DDPM table's entry for a discrete VP score function)
+        const float x0h = tweedie_x0(a.xt[s * a.Dpad + c], sigma2, score, alpha);
         const float diff = a.x0[i] - x0h;
         acc += w * (diff * diff);
         if (a.x0_hat) a.x0_hat[i] = x0h;
@@ -483,7 +486,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_ddim_step(WithSde
     float w = 0.5f;
     if (a.last && a.weighted) {
         const SdeAt a0 = sde_at(d.sde, a.t0);
-        w = 0.5f * sqrtf(1.0f + a0.mc / a0.sd);                       // completion.py:128,143
+        w = snr_loss_weight(a0.mc / a0.sd);                           // completion.py:128,143
     }
     float acc = 0.f;
     const int64_t total = a.Bpad * qx;
@@ -497,8 +500,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_ddim_step(WithSde
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (c + r >= a.D) continue;
-                const float model = r4[r] / usig;
-                const float score = sde_score(d.sde, model, at.sd_score);     // utils.py:155,162 / :160 / :180
+                const float score = score_of_res(d.sde, r4[r], usig, at.sd_score);
                 const float noise = -score * s_c;                             // completion.py:122
                 const float x = ratio * (x4[r] - s_c * noise) + s_b * noise;  // :123-126
                 xn[r] = x;
@@ -562,9 +564,8 @@ template <typename T> __global__ void __launch_bounds__(256) k_dpm_update(WithSd
                 if (c + r >= a.D) continue;
                 const int64_t o = s * a.D + c + r;
                 const float x0 = a.x[o];
-                const float model = r4[r] / usig;
-                const float score = sde_score(d.sde, model, at.sd_score);     // utils.py:155,162 / :180
-                const float Di = (x0 + sigma2 * score) / alpha;               // completion.py:107
+                const float score = score_of_res(d.sde, r4[r], usig, at.sd_score);
+                const float Di = tweedie_x0(x0, sigma2, score, alpha);
                 float x = a.cx * x0 + a.c0 * Di;
                 if (a.use_hist) x = x + a.c1 * a.hist[o];
                 if (a.hist) a.hist[o] = Di;
@@ -605,8 +606,7 @@ __global__ void __launch_bounds__(256) k_red_diff(WithSde<RedDiffArgs> d) {
             if (c + r >= a.D) continue;
             const int64_t o = s * a.D + c + r;
             const float z = a.z_in ? a.z_in[o] : n4[r];
-            const float model = r4[r] / usig;
-            const float score = sde_score(d.sde, model, at.sd_score);
+            const float score = score_of_res(d.sde, r4[r], usig, at.sd_score);
             const float eps = -score * sigma;                         // :150 score to noise prediction
             const float dz = eps - z;
             acc += dz * a.x0[o];
@@ -635,15 +635,13 @@ __global__ void __launch_bounds__(256) k_completion_update(WithSde<CompletionUpd
     const float alpha = at.mc, sigma = at.sd;                         // return_alpha_sigma, sde_lib.py:227-231
     const float sigma2 = sigma * sigma;
     const float usig = launch_usig(a, at.label);
-    const float snr = alpha / sqrtf(sigma2);                          // completion.py:108
-    const float w = a.weighted ? 0.5f * sqrtf(1.0f + snr) : 0.5f;     // completion.py:143-146
+    const float w = a.weighted ? snr_loss_weight(alpha / sqrtf(sigma2)) : 0.5f;     // completion.py:108,143-146
     const int64_t total = a.B * a.D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t s = i / a.D;
         const int c = (int)(i % a.D);
-        const float model = a.res[s * a.Cp + c] / usig;
-        const float score = sde_score(d.sde, model, at.sd_score);     // utils.py:155,162 / :160
-        const float x0h = (a.xt[s * a.Dpad + c] + sigma2 * score) / alpha;   // completion.py:107
+        const float score = score_of_res(d.sde, a.res[s * a.Cp + c], usig, at.sd_score);
+        const float x0h = tweedie_x0(a.xt[s * a.Dpad + c], sigma2, score, alpha);
         float x = a.x[i];
         const float mk = a.mask[i];
         const float g_prior = ((2.0f * w) * (x - x0h) * a.inv_n) * a.w_prior;
@@ -668,9 +666,6 @@ hipError_t launch_completion_update(const CompletionUpdateArgs& a, hipStream_t s
 //   x_mean = x + step * grad;   x = x_mean + sqrt(2 step) * noise
 // Two passes around the grid-wide (and, under data parallelism, cross-rank) mean: norms -> [all-reduce of two scalars] -> update.
 // Both recompute score and noise from the same inputs / Philox counters, so nothing but the two sums travels between them.
-__device__ __forceinline__ float langevin_score(const SdeDev& sde, float res, float usig, float sd) {
-    return sde_score(sde, res / usig, sd);                          // model.py:194, utils.py:155,162
-}
 __global__ void __launch_bounds__(256) k_langevin_norms(WithSde<LangevinArgs> d) {
     const LangevinArgs& a = d.a;
     const int QD = (a.D + 3) >> 2;
@@ -687,7 +682,7 @@ __global__ void __launch_bounds__(256) k_langevin_norms(WithSde<LangevinArgs> d)
             for (int r = 0; r < 4; ++r) {
                 const int c = q * 4 + r;
                 if (c >= a.D) continue;
-                const float g = langevin_score(d.sde, a.res[s * a.Cp + c], usig, sd);
+                const float g = score_of_res(d.sde, a.res[s * a.Cp + c], usig, sd);
                 const float n = a.noise ? a.noise[s * a.D + c] : z[r];
                 g2 += g * g;
                 n2 += n * n;
@@ -742,7 +737,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_langevin_update(W
             for (int r = 0; r < 4; ++r) {
                 if (c + r >= a.D) continue;
                 const int64_t o = s * a.D + c + r;
-                const float g = langevin_score(d.sde, a.res[s * a.Cp + c + r], usig, sd);
+                const float g = score_of_res(d.sde, a.res[s * a.Cp + c + r], usig, sd);
                 const float n = a.noise ? a.noise[o] : z[r];
                 const float xm = a.x[o] + step * g;                   // :299
                 const float x = xm + nscale * n;                      // :300
@@ -786,7 +781,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_pc_pred_update(Wi
                 const int64_t o = s * a.D + c + r;
                 float x = a.x[o];
                 float score = 0.f;
-                if (score_read) score = sde_score(d.sde, a.res[s * a.Cp + c + r] / usig, at.sd_score);   // model.py:194, utils.py:162
+                if (score_read) score = score_of_res(d.sde, a.res[s * a.Cp + c + r], usig, at.sd_score);
                 const float z = (draws && a.z_pred) ? a.z_pred[o] : zp[r];
                 float x_mean;
                 x = pc_pred_step(d.sde, a.tab, ks, a.pred, a.pf, x, score, z, &x_mean);
@@ -829,7 +824,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_ald_update(WithSd
             for (int r = 0; r < 4; ++r) {
                 if (c + r >= a.D) continue;
                 const int64_t o = s * a.D + c + r;
-                const float g = sde_score(d.sde, a.res[s * a.Cp + c + r] / usig, at.sd_score);
+                const float g = score_of_res(d.sde, a.res[s * a.Cp + c + r], usig, at.sd_score);
                 const float n = a.noise ? a.noise[o] : z[r];
                 const float xm = a.x[o] + step * g;                   // :336
                 float x = xm + n * nscale;                            // :337
@@ -863,8 +858,8 @@ template <typename A> __device__ __forceinline__ GuidedScal guided_scalars(const
 }
 // r = obs mask - y0 mask and the score, for one element
 __device__ __forceinline__ float guided_resid(const SdeDev& sde, const GuidedScal& k, float res, float x, float obs, float m, float* score_out) {
-    const float score = sde_score(sde, res / k.usig, k.sds);                       // model.py:194, utils.py:162
-    const float y0 = (x + k.sd2 * score) / k.mc;                                    // sampling.py:200
+    const float score = score_of_res(sde, res, k.usig, k.sds);
+    const float y0 = tweedie_x0(x, k.sd2, score, k.mc);                             // sampling.py:200
     *score_out = score;
     return obs * m - y0 * m;                                                        // :201
 }

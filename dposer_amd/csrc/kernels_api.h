@@ -117,20 +117,27 @@ hipError_t launch_em_update(const EmUpdateArgs& a, hipStream_t st);
 // fp32 FT [Bpad][Dpad] -> row-major [B][D] (end of the fused sampler fast path); any of the two pairs may be null
 hipError_t launch_ft_to_rows(const float* a_ft, float* a, const float* b_ft, float* b, int64_t B, int64_t Bpad, int D, int Dpad, hipStream_t st);
 
-struct DenoiseArgs {       // one_step_denoise + prior loss (run/completion.py:105-149, run/smplify.py:69-107)
-    const float* res;      // [Bpad][Cp]
+// What the prior and loop kernels that read the network output at one shared t have in common (scorefc.hip: score_out fills it from the call
+// context).  UpdateCommon's care: the pointers first, t with them, no padding hole, and the size a multiple of 8, so that the derived
+// blocks start their own pointers right behind it and a kernel's first batch of scalar loads covers the block from its start.
+struct ScoreOut {
+    const float* res;      // [Bpad][Cp] post_dense output at x_t
+    const float* sigmas;
+    float t;               // the launch's shared time
+    int scale_by_sigma;
+    int64_t B;
+    int D, Dpad, Cp, num_scales;
+    SdeCfg sde;
+};
+static_assert(sizeof(ScoreOut) == 2 * 8 + 2 * 4 + 8 + 4 * 4 + sizeof(SdeCfg), "ScoreOut has a padding hole");
+struct DenoiseArgs : ScoreOut {   // one_step_denoise + prior loss (run/completion.py:105-149, run/smplify.py:69-107)
     const float* x0;       // [B][D]
     const float* xt;       // [B][Dpad] perturbed data (fp32 row-major)
-    const float* sigmas;
     float* x0_hat;         // [B][D] or null
     float* grad;           // [B][D] d loss / d x0 (analytic, x0_hat detached) or null
     float* loss_part;      // per-block partial sums
-    float t;
     float inv_n;           // 1/n of the reduction (mean: 1/(B*D), sum/batch: 1/B)
     int weighted;
-    int64_t B;
-    int D, Dpad, Cp, num_scales, scale_by_sigma;
-    SdeCfg sde;
 };
 hipError_t launch_denoise(const DenoiseArgs& a, int* nblocks, hipStream_t st);
 
@@ -148,23 +155,21 @@ struct PerturbSharedArgs { // x_t = mean + std*z at one shared t; writes xin (FT
 };
 hipError_t launch_perturb_shared(const PerturbSharedArgs& a, hipStream_t st);
 
-struct DdimStepArgs {      // one step of multi_step_denoise behind its network evaluation (run/completion.py:112-129); the last step also forms the loss
-    const float* res;      // [Bpad][Cp] model output at x_t
+struct DdimStepArgs : ScoreOut {   // one step of multi_step_denoise behind its network evaluation (run/completion.py:112-129); the last step also forms the loss
+    // t: time_traj[i]
     float* xt;             // [Bpad][Dpad] current state (fp32 row-major), updated in place
     void* xin;             // FT [Bpad][Dpad]: the next evaluation's network input
-    const float* sigmas;
     const float* x0;       // last step: [B][D] clean poses
     float* x0_hat;         // last step: [B][D] the multi-step estimate, or null
     float* grad;           // last step: [B][D] d loss / d x0 (the estimate is detached) or null
     float* loss_part;      // last step: per-block partial sums
-    float t, t_next;       // time_traj[i], time_traj[i + 1]
+    int64_t Bpad;
+    float t_next;          // time_traj[i + 1]
     float t0;              // time_traj[0]: the SNR of the loss weight (completion.py:127-128)
     float inv_n;
     int weighted;
     int last;              // 1: no state is written back; x0_hat / grad / loss_part are
-    int64_t B, Bpad;
-    int D, Dpad, Cp, num_scales, scale_by_sigma, f32;
-    SdeCfg sde;
+    int f32;
 };
 hipError_t launch_ddim_step(const DdimStepArgs& a, int* nblocks, hipStream_t st);
 
@@ -182,41 +187,29 @@ struct DpmUpdateArgs : UpdateCommon {   // one DPM-Solver++ (multistep, data pre
 };
 hipError_t launch_dpm_update(const DpmUpdateArgs& a, hipStream_t st);
 
-struct RedDiffArgs {       // MotionDenoise.RED_Diff behind its network evaluation (run/motion_denoising.py:145-154)
-    const float* res;      // [Bpad][Cp] model output at x_t
+struct RedDiffArgs : ScoreOut {   // MotionDenoise.RED_Diff behind its network evaluation (run/motion_denoising.py:145-154)
     const float* x0;       // [B][D]
     const float* z_in;     // the perturbation's injected z, or null (-> the same Philox STREAM_PRIOR draws as k_perturb_shared)
-    const float* sigmas;
     float* eps_pred;       // [B][D] noise prediction -score * std, or null
     float* grad;           // [B][D] weight (eps_pred - z) inv_batch, or null
     float* loss_part;      // per-block partial sums
-    float t;
-    float inv_batch;
-    int64_t B;
-    int D, Cp, num_scales, scale_by_sigma;
-    SdeCfg sde;
     uint64_t seed;
+    float inv_batch;
     uint32_t step;
 };
 hipError_t launch_red_diff(const RedDiffArgs& a, int* nblocks, hipStream_t st);
 
-struct CompletionUpdateArgs {   // one optimisation step of DPoserComp.optimize (run/completion.py:167-207) after the network evaluation
-    const float* res;      // [Bpad][Cp] model output at x_t
+struct CompletionUpdateArgs : ScoreOut {   // one optimisation step of DPoserComp.optimize (run/completion.py:167-207) after the network evaluation
     const float* xt;       // [Bpad][Dpad] perturbed data
     const float* obs;      // [B][D]
     const float* mask;     // [B][D]
-    const float* sigmas;
     float* x;              // [B][D] optimisation variable, updated in place
     float* m;              // [B][D] Adam first moment
     float* v;              // [B][D] Adam second moment
-    float t;
     float inv_n;           // 1 / (B * D): both losses are means over the batch (completion.py:147, nn.MSELoss)
     float w_prior, w_data; // loss weights of this step (completion.py:151-155)
     int weighted;
     AdamScalars s;         // torch.optim.Adam scalars of this step
-    int64_t B;
-    int D, Dpad, Cp, num_scales, scale_by_sigma;
-    SdeCfg sde;
 };
 hipError_t launch_completion_update(const CompletionUpdateArgs& a, hipStream_t st);
 

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -715,12 +716,17 @@ static int run_temb(dposer_scorefc_s* h, const float* flat, const char* packed, 
 // scale_by_sigma as the shared-t kernels take it: 0 off, 1 divide by sigmas[(int)label] (positional embedding, model.py:159), 2 divide by the
 // label itself (Fourier embedding: used_sigmas = t, model.py:152)
 static inline int sbs_mode(const dposer_scorefc_s* h) { return h->d.scale_by_sigma ? (h->d.embedding == DPOSER_EMB_FOURIER ? 2 : 1) : 0; }
-static int check_common(dposer_scorefc_t h, const float* flat, const void* packed, void* ws, int64_t batch) {
-    DP_CHECK_ARG(h && flat && packed && ws, "null argument");
+// DP_CHECK_ARG for the bodies that several entry points share: the message carries the name of the entry that was called
+#define DP_CHECK_ARG_AS(entry, cond, msg)                                      \
+    do {                                                                       \
+        if (!(cond)) return dposer_set_error(DPOSER_ERR_BAD_ARG, std::string(entry) + ": " + (msg)); \
+    } while (0)
+static int check_common(dposer_scorefc_t h, const float* flat, const void* packed, void* ws, int64_t batch, const char* entry = "check_common") {
+    DP_CHECK_ARG_AS(entry, h && flat && packed && ws, "null argument");
     g_act = h->d.activation;
-    DP_CHECK_ARG(batch > 0, "batch must be positive");
-    DP_CHECK_ARG(((uintptr_t)flat & 15) == 0, "flat_params must be 16-byte aligned");
-    DP_CHECK_ARG(((uintptr_t)packed & 255) == 0 && ((uintptr_t)ws & 255) == 0, "packed / workspace must be 256-byte aligned");
+    DP_CHECK_ARG_AS(entry, batch > 0, "batch must be positive");
+    DP_CHECK_ARG_AS(entry, ((uintptr_t)flat & 15) == 0, "flat_params must be 16-byte aligned");
+    DP_CHECK_ARG_AS(entry, ((uintptr_t)packed & 255) == 0 && ((uintptr_t)ws & 255) == 0, "packed / workspace must be 256-byte aligned");
     return DPOSER_OK;
 }
 
@@ -864,15 +870,72 @@ static int build_time_table_at(dposer_scorefc_s* h, const float* flat, const cha
     DP_TRY(stage_step_labels(h, w, s, &t, 1, st));
     return build_time_table(h, flat, packed, w, w.tt_labels, 0.f, 1, freq, st);
 }
-// the fields the samplers' update kernels share (kernels_api.h), from the handle, the workspace and the call
-static UpdateCommon update_common(dposer_scorefc_s* h, const Ws& w, const dposer_sde_desc* sde, const float* sigmas, float* x, float* x_mean,
-                                  uint64_t seed, int64_t B) {
-    UpdateCommon c{};
-    c.res = w.res; c.x = x; c.x_mean = x_mean; c.xin = w.xin; c.sigmas = sigmas;
-    c.B = B; c.Bpad = w.Bpad; c.D = h->D; c.Dpad = h->Dpad; c.Cp = h->Cp; c.num_scales = h->d.num_scales;
-    c.f32 = h->f32; c.scale_by_sigma = sbs_mode(h); c.sde = to_sde(sde); c.seed = seed;
-    return c;
+// ---- the call context of the shared-t entry points ------------------------------------------------------------------------------------
+// What every body that evaluates the network at a time shared by the whole batch derives at its top, and the steps they all take.  One rule:
+// every argument check comes first -- check(), then the entry's own, the descriptor's among them, in the order the entry always had them --
+// and only then open(): a refused call opens no roctx range and launches nothing, and its message names the extern "C" entry that was called.
+// open() takes the checked descriptor (null: dposer_prior_table_build) and lays the workspace out; with zero table rows that is pointer
+// arithmetic only, and the entries that may be asked for zero steps return right behind it.
+namespace {
+struct SharedT {
+    const char* entry = nullptr;
+    dposer_scorefc_s* h = nullptr;
+    const float* flat = nullptr;
+    const char* packed = nullptr;
+    char* ws = nullptr;
+    hipStream_t st = nullptr;
+    int64_t B = 0;
+    const dposer_sde_desc* sde = nullptr;
+    SdeCfg sc{};
+    Ws w;
+    std::optional<DpRange> range;              // (not copyable: nor is the context)
+    int check(const char* entry_, dposer_scorefc_t h_, const float* flat_, const void* packed_, void* ws_, int64_t B_, void* stream) {
+        DP_TRY(check_common(h_, flat_, packed_, ws_, B_, entry = entry_));
+        h = h_; flat = flat_; packed = (const char*)packed_; ws = (char*)ws_; B = B_; st = (hipStream_t)stream;
+        return DPOSER_OK;
+    }
+    void open(const dposer_sde_desc* s, int ws_kind, int table_rows) {
+        if ((sde = s)) sc = to_sde(s);
+        range.emplace(entry);
+        g_alg_batch = B;
+        layout_ws(h, B, ws_kind, table_rows, ws, w);
+    }
+    // the time-bias rows of the n step times `times_host` (labels = t * 999, utils.py:152; VE: sigma(t), formed on the device), one H2D copy
+    int table(const float* times_host, int n, const float* freq) {
+        DP_TRY(stage_step_labels(h, w, sde, times_host, n, st));
+        return build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n, freq, st);
+    }
+    int table_at(float t, const float* freq) { return build_time_table_at(h, flat, packed, w, sde, t, freq, st); }
+    int eval(int64_t row) { return run_shared_t(h, flat, packed, w, row, B, st); }      // xin -> res on table row `row`
+    // x_t = mean + std z at t into w.xin (FT) and w.xt (fp32 rows); z == null: Philox STREAM_PRIOR at (seed, step)
+    int perturb(const float* x0, const float* z, float t, uint64_t seed, uint32_t step) {
+        PerturbSharedArgs pa;
+        pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
+        pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
+        DP_CHECK_HIP(launch_perturb_shared(pa, st));
+        return DPOSER_OK;
+    }
+};
+}  // namespace
+// the fields the samplers' update kernels share (kernels_api.h), from the context and the call
+static UpdateCommon update_common(const SharedT& c, const float* sigmas, float* x, float* x_mean, uint64_t seed) {
+    UpdateCommon u{};
+    u.res = c.w.res; u.x = x; u.x_mean = x_mean; u.xin = c.w.xin; u.sigmas = sigmas;
+    u.B = c.B; u.Bpad = c.w.Bpad; u.D = c.h->D; u.Dpad = c.h->Dpad; u.Cp = c.h->Cp; u.num_scales = c.h->d.num_scales;
+    u.f32 = c.h->f32; u.scale_by_sigma = sbs_mode(c.h); u.sde = c.sc; u.seed = seed;
+    return u;
 }
+// the same for the prior and loop kernels that read the network output at t (kernels_api.h: ScoreOut)
+static ScoreOut score_out(const SharedT& c, const float* sigmas, float t) {
+    ScoreOut o{};
+    o.res = c.w.res; o.sigmas = sigmas; o.t = t; o.scale_by_sigma = sbs_mode(c.h); o.B = c.B;
+    o.D = c.h->D; o.Dpad = c.h->Dpad; o.Cp = c.h->Cp; o.num_scales = c.h->d.num_scales; o.sde = c.sc;
+    return o;
+}
+// the range [start_step, start_step + n_steps) of an N-step grid, cut at its end; n_steps < 0: to the end
+static inline int steps_to_run(int N, int start_step, int n_steps) { return (n_steps < 0 || n_steps > N - start_step) ? N - start_step : n_steps; }
+// the trajectory slot loop index i writes ([B][D] slots, one every `stride` steps), or null
+static inline float* traj_slot(float* traj, int i, int stride, int64_t BD) { return (traj && ((i + 1) % stride == 0)) ? traj + (int64_t)((i + 1) / stride - 1) * BD : nullptr; }
 // sum_b ||grad_b|| and sum_b ||noise_b|| of the call's samples -> norm_sums[0..1]
 static int langevin_norm_sums(const LangevinArgs& a, float* norm_sums, hipStream_t st) {
     int nb = 0;
@@ -889,44 +952,38 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
                    const dposer_pc_desc* pc, float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
                    const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj, int32_t traj_stride,
                    const float* disc_table_host, float* norm_sums, const float* freq, const float* sigmas, int64_t B, void* stream) {
-    DP_CHECK_ARG(pc, "null argument");
+    DP_CHECK_ARG_AS(entry, pc, "null argument");
     const int pred = pc->predictor, corr = pc->corrector, pf = pc->probability_flow ? 1 : 0;
-    DP_CHECK_ARG(pred == DPOSER_PC_PRED_NONE || pred == DPOSER_PC_PRED_EULER_MARUYAMA || pred == DPOSER_PC_PRED_REVERSE_DIFFUSION || pred == DPOSER_PC_PRED_ANCESTRAL, "unknown predictor kind");
-    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || corr == DPOSER_PC_CORR_LANGEVIN || corr == DPOSER_PC_CORR_ALD, "unknown corrector kind");
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
-    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
-    DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
-    DP_CHECK_ARG((observation == nullptr) == (mask == nullptr), "observation and mask go together");
-    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
+    DP_CHECK_ARG_AS(entry, pred == DPOSER_PC_PRED_NONE || pred == DPOSER_PC_PRED_EULER_MARUYAMA || pred == DPOSER_PC_PRED_REVERSE_DIFFUSION || pred == DPOSER_PC_PRED_ANCESTRAL, "unknown predictor kind");
+    DP_CHECK_ARG_AS(entry, corr == DPOSER_PC_CORR_NONE || corr == DPOSER_PC_CORR_LANGEVIN || corr == DPOSER_PC_CORR_ALD, "unknown corrector kind");
+    SharedT c;
+    DP_TRY(c.check(entry, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG_AS(entry, sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
+    DP_CHECK_ARG_AS(entry, sde_kind_ok(sde), "unknown SDE kind");
+    DP_CHECK_ARG_AS(entry, sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
+    DP_CHECK_ARG_AS(entry, (observation == nullptr) == (mask == nullptr), "observation and mask go together");
+    DP_CHECK_ARG_AS(entry, traj_stride >= 1, "traj_stride must be >= 1");
     const SdeCfg sc = to_sde(sde);
     if (pred == DPOSER_PC_PRED_ANCESTRAL) {      // AncestralSamplingPredictor.__init__, sampling.py:227-231
         if (sc.kind == SDE_SUBVP) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "ancestral sampling supports the VE and VP SDEs only");
         if (pf) return dposer_set_error(DPOSER_ERR_UNSUPPORTED, "probability flow is not supported by ancestral sampling");
     }
-    DP_CHECK_ARG(corr == DPOSER_PC_CORR_NONE || pc->n_steps_each >= 1, "n_steps_each must be >= 1 with a corrector");
-    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || norm_sums, "norm_sums is required by the Langevin corrector");
-    DP_CHECK_ARG(corr != DPOSER_PC_CORR_LANGEVIN || pc->inv_global_batch > 0.0, "inv_global_batch must be > 0 for the Langevin corrector");
+    DP_CHECK_ARG_AS(entry, corr == DPOSER_PC_CORR_NONE || pc->n_steps_each >= 1, "n_steps_each must be >= 1 with a corrector");
+    DP_CHECK_ARG_AS(entry, corr != DPOSER_PC_CORR_LANGEVIN || norm_sums, "norm_sums is required by the Langevin corrector");
+    DP_CHECK_ARG_AS(entry, corr != DPOSER_PC_CORR_LANGEVIN || pc->inv_global_batch > 0.0, "inv_global_batch must be > 0 for the Langevin corrector");
     const bool pred_table = pred == DPOSER_PC_PRED_ANCESTRAL || (pred == DPOSER_PC_PRED_REVERSE_DIFFUSION && sc.kind != SDE_SUBVP);
     const bool corr_table = corr != DPOSER_PC_CORR_NONE && sc.kind != SDE_VE;
-    DP_CHECK_ARG(!(pred_table || corr_table) || disc_table_host, "disc_table_host is required: the predictor or corrector reads the SDE's discrete table");
-    DpRange _dp_range(entry);                        // (every argument check is above: a refused call opens no range and launches nothing)
-    g_alg_batch = B;
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    const int N = sde->N;
-    const int n_run = (n_steps < 0 || n_steps > N - start_step) ? N - start_step : n_steps;   // (a range ends without look-ahead imputation)
+    DP_CHECK_ARG_AS(entry, !(pred_table || corr_table) || disc_table_host, "disc_table_host is required: the predictor or corrector reads the SDE's discrete table");
+    const int n_run = steps_to_run(sde->N, start_step, n_steps);      // (a range ends without look-ahead imputation)
+    c.open(sde, DPOSER_WS_SHARED_T, n_run);
     if (n_run == 0) return DPOSER_OK;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, n_run, (char*)ws_, w);
-    // labels = t * 999 (utils.py:152; VE: sigma(t), on the device), one H2D copy
-    DP_TRY(stage_step_labels(h, w, sde, timesteps_host + start_step, n_run, st));
-    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_run, freq, st));
-
+    Ws& w = c.w;
+    hipStream_t st = c.st;
+    DP_TRY(c.table(timesteps_host + start_step, n_run, freq));
     const int nc = corr == DPOSER_PC_CORR_NONE ? 0 : pc->n_steps_each;
     const int k_noise = nc + (observation ? 3 : 1);
     const int64_t BD = B * h->D;
-    const UpdateCommon uc = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
+    const UpdateCommon uc = update_common(c, sigmas, x, x_mean, seed);
     EmUpdateArgs ea{};                            // Euler-Maruyama predictor, and the stand-alone "imputation + pack" launch
     static_cast<UpdateCommon&>(ea) = uc; ea.obs = observation; ea.mask = mask; ea.pf = pf;
     PcPredArgs pa{};
@@ -958,9 +1015,9 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
             const int gi = start_step + i;
             const void* last = nullptr;
             const Planes* last_pl = nullptr;
-            DP_TRY(run_shared_t_layers(h, flat, packed, w, i, st, &last, &last_pl));
+            DP_TRY(run_shared_t_layers(h, flat, c.packed, w, i, st, &last, &last_pl));
             g_next_flops = 2.0 * (double)B * h->D * h->H;
-            GemmArgs g = gemm_args(packed + h->pk_wpost, h->H / h->KBS * h->wk, h->Cp / (shape_ct(shape) * 32), (int)(w.Bpad / (shape_st(shape) * 32)));
+            GemmArgs g = gemm_args(c.packed + h->pk_wpost, h->H / h->KBS * h->wk, h->Cp / (shape_ct(shape) * 32), (int)(w.Bpad / (shape_st(shape) * 32)));
             add_act(h, g, last, *last_pl, h->H / h->KBS);
             EmStepParams p;
             std::memset(&p, 0, sizeof(p));
@@ -980,7 +1037,7 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
         const PcTab tab = make_pc_tab(sc, disc_table_host, t);
         const float alpha = (corr_table) ? 1.0f - tab.tab : 1.0f;                 // sampling.py:287-291: sde.alphas = 1 - discrete_betas, fp32
         for (int k = 0; k < nc; ++k) {
-            DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+            DP_TRY(c.eval(i));
             const float* zc = nz ? nz + (int64_t)k * BD : nullptr;
             const uint32_t cstep = (uint32_t)((int64_t)gi * nc + k);
             if (corr == DPOSER_PC_CORR_LANGEVIN) {
@@ -1005,14 +1062,14 @@ static int pc_loop(const char* entry, dposer_scorefc_t h, const float* flat, con
         const float* z_pred = nz ? nz + (int64_t)(nc + (observation ? 1 : 0)) * BD : nullptr;
         const float* z_impB = (nz && observation) ? nz + (int64_t)(nc + 2) * BD : nullptr;
         const float* z_impA = (nz && observation && ahead) ? nz + (int64_t)k_noise * BD : nullptr;
-        float* slot = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
+        float* slot = traj_slot(traj, i, traj_stride, BD);
         if (pred == DPOSER_PC_PRED_EULER_MARUYAMA) {
-            DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+            DP_TRY(c.eval(i));
             ea.res = w.res; ea.t = t; ea.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; ea.step = (uint32_t)gi;
             ea.z_pred = z_pred; ea.z_impB = z_impB; ea.z_impA = z_impA; ea.traj = slot;
             DP_CHECK_HIP(launch_em_update(ea, st));
         } else {
-            if (pred != DPOSER_PC_PRED_NONE) DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+            if (pred != DPOSER_PC_PRED_NONE) DP_TRY(c.eval(i));
             pa.t = t; pa.t_next = ahead ? timesteps_host[gi + 1] : -1.0f; pa.step = (uint32_t)gi; pa.tab = tab;
             pa.z_pred = z_pred; pa.z_impB = z_impB; pa.z_impA = z_impA; pa.traj = slot;
             DP_CHECK_HIP(launch_pc_pred_update(pa, st));
@@ -1127,39 +1184,34 @@ extern "C" int dposer_dpm_coefficients(const dposer_sde_desc* sde, const double*
 }
 
 // The few-step sampler: every step is one network evaluation on its time-table row + k_dpm_update, which leaves the new state (imputed at
-// the next time under a completion) FT-tiled in w.xin.  Host loop in pc_loop's manner; the schedule is formed before anything is launched.
+// the next time under a completion) FT-tiled in w.xin.  The schedule is formed with the argument checks, before the context opens.
 extern "C" int dposer_dpm_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                   const dposer_dpm_desc* dpm, float* x, float* x0_hat, float* hist, const float* times_host, int32_t n_steps,
                                   const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
                                   int32_t traj_stride, const float* freq, const float* sigmas, int64_t B, void* stream) {
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    DP_CHECK_ARG(sde && dpm && x && times_host && freq && sigmas, "null argument");
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG(sde && dpm && x && times_host && freq && sigmas, "null argument");      // (the descriptor's kind: dpm_schedule)
     DP_CHECK_ARG((observation == nullptr) == (mask == nullptr), "observation and mask go together");
     DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
     DP_CHECK_ARG(dpm->order != 2 || hist, "hist is required at order 2");
     std::vector<double> coef(3 * (size_t)(n_steps > 0 ? n_steps : 1));
     DP_TRY(dpm_schedule(__func__, sde, [&](int i) { return (double)times_host[i]; }, n_steps, dpm->order, dpm->lower_order_final, coef.data()));
-    DP_RANGE();                                      // (every argument check is above: a refused call opens no range and launches nothing)
-    g_alg_batch = B;
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, n_steps, (char*)ws_, w);
-    DP_TRY(stage_step_labels(h, w, sde, times_host, n_steps, st));      // the network is evaluated at s_0 .. s_{n-1}
-    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_steps, freq, st));
+    c.open(sde, DPOSER_WS_SHARED_T, n_steps);
+    DP_TRY(c.table(times_host, n_steps, freq));                          // the network is evaluated at s_0 .. s_{n-1}
     const int64_t BD = B * h->D;
-    const UpdateCommon uc = update_common(h, w, sde, sigmas, x, nullptr, seed, B);
+    const UpdateCommon uc = update_common(c, sigmas, x, nullptr, seed);
     {   // imputation at s_0 (completion) + pack x: k_em_update's stand-alone form, its draw STREAM_IMPUTE_A keyed at 0
         EmUpdateArgs ea{};
         static_cast<UpdateCommon&>(ea) = uc; ea.obs = observation; ea.mask = mask;
         ea.res = nullptr; ea.t = times_host[0]; ea.t_next = times_host[0]; ea.step = (uint32_t)-1;
         ea.z_impA = (noise && observation) ? noise : nullptr;
-        DP_CHECK_HIP(launch_em_update(ea, st));
+        DP_CHECK_HIP(launch_em_update(ea, c.st));
     }
     DpmUpdateArgs da{};
     static_cast<UpdateCommon&>(da) = uc; da.obs = observation; da.mask = mask; da.hist = hist;
     for (int i = 0; i < n_steps; ++i) {
-        DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+        DP_TRY(c.eval(i));
         const bool last = i + 1 == n_steps;
         const bool ahead = observation && !last;
         da.t = times_host[i]; da.t_next = ahead ? times_host[i + 1] : -1.0f; da.step = (uint32_t)i;
@@ -1167,8 +1219,8 @@ extern "C" int dposer_dpm_sampler(dposer_scorefc_t h, const float* flat, const v
         da.use_hist = dpm_effective_order(dpm->order, dpm->lower_order_final, i, n_steps) == 2;
         da.z_imp = (noise && ahead) ? noise + (int64_t)(i + 1) * BD : nullptr;
         da.x0_hat = last ? x0_hat : nullptr;
-        da.traj = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
-        DP_CHECK_HIP(launch_dpm_update(da, st));
+        da.traj = traj_slot(traj, i, traj_stride, BD);
+        DP_CHECK_HIP(launch_dpm_update(da, c.st));
     }
     return DPOSER_OK;
 }
@@ -1182,95 +1234,83 @@ extern "C" int dposer_langevin_step(dposer_scorefc_t h, const float* flat, const
                                     float* x, float* x_mean, float t, float alpha, float snr, const float* noise, uint64_t seed,
                                     uint32_t step, float* norm_sums, int32_t phase, double inv_global_batch, const float* freq,
                                     const float* sigmas, int64_t B, void* stream) {
-    DP_RANGE();
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
     DP_CHECK_ARG(sde && x && norm_sums && freq && sigmas, "null argument");
     DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
     DP_CHECK_ARG(phase == 0 || phase == 1, "phase must be 0 (norms) or 1 (update)");
     DP_CHECK_ARG(phase == 0 || x_mean, "x_mean is required in the update phase");
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, 1, (char*)ws_, w);
+    c.open(sde, DPOSER_WS_SHARED_T, 1);
+    const Ws& w = c.w;
     LangevinArgs a{};
-    static_cast<UpdateCommon&>(a) = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
+    static_cast<UpdateCommon&>(a) = update_common(c, sigmas, x, x_mean, seed);
     a.xin = nullptr;                              // (the predictor call that follows packs the state)
     a.noise = noise; a.part = w.loss_part; a.norm_sums = norm_sums;
     a.t = t; a.alpha = alpha; a.snr = snr; a.inv_global_batch = (float)inv_global_batch; a.step = step;
     if (phase == 0) {
-        DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
-        DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
-        DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
-        DP_TRY(langevin_norm_sums(a, norm_sums, st));
+        DP_TRY(c.table_at(t, freq));
+        DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, c.st));
+        DP_TRY(c.eval(0));
+        DP_TRY(langevin_norm_sums(a, norm_sums, c.st));
     } else {
-        DP_CHECK_HIP(launch_langevin_update(a, st));
+        DP_CHECK_HIP(launch_langevin_update(a, c.st));
     }
     return DPOSER_OK;
 }
 
 // table_rows <= 0: the time-bias row is built for this call (one row).  table_rows > 0: row `row` of a table that
 // dposer_prior_table_build wrote into the same workspace (laid out for table_rows rows) -- the task loops build it once.
-static int prior_loss_impl(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+static int prior_loss_impl(const char* entry, dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                            const float* x0, const float* z, float t, int32_t weighted, float inv_n, float* x0_hat, float* grad,
                            float* loss, uint64_t seed, uint32_t step, const float* freq, const float* sigmas, int64_t B, void* stream,
                            int32_t row, int32_t table_rows) {
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
-    DP_CHECK_ARG(sde && x0 && loss && sigmas && (freq || table_rows > 0), "null argument");
-    DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
-    DP_CHECK_ARG(table_rows <= 0 || (row >= 0 && row < table_rows), "table row out of range");
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, table_rows > 0 ? table_rows : 1, (char*)ws_, w);
-    if (table_rows <= 0) DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
-    const SdeCfg sc = to_sde(sde);
-    PerturbSharedArgs pa;
-    pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
-    pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
-    DP_CHECK_HIP(launch_perturb_shared(pa, st));
-    DP_TRY(run_shared_t(h, flat, packed, w, table_rows > 0 ? row : 0, B, st));
-    DenoiseArgs da;
-    da.res = w.res; da.x0 = x0; da.xt = w.xt; da.sigmas = sigmas; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = w.loss_part;
-    da.t = t; da.inv_n = inv_n; da.weighted = weighted; da.B = B; da.D = h->D; da.Dpad = h->Dpad; da.Cp = h->Cp;
-    da.num_scales = h->d.num_scales; da.scale_by_sigma = sbs_mode(h); da.sde = sc;
+    SharedT c;
+    DP_TRY(c.check(entry, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG_AS(entry, sde && x0 && loss && sigmas && (freq || table_rows > 0), "null argument");
+    DP_CHECK_ARG_AS(entry, sde_kind_ok(sde), "unknown SDE kind");
+    DP_CHECK_ARG_AS(entry, table_rows <= 0 || (row >= 0 && row < table_rows), "table row out of range");
+    c.open(sde, DPOSER_WS_SHARED_T, table_rows > 0 ? table_rows : 1);
+    if (table_rows <= 0) DP_TRY(c.table_at(t, freq));
+    DP_TRY(c.perturb(x0, z, t, seed, step));
+    DP_TRY(c.eval(table_rows > 0 ? row : 0));
+    DenoiseArgs da{};
+    static_cast<ScoreOut&>(da) = score_out(c, sigmas, t);
+    da.x0 = x0; da.xt = c.w.xt; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = c.w.loss_part; da.inv_n = inv_n; da.weighted = weighted;
     int nb = 0;
-    DP_CHECK_HIP(launch_denoise(da, &nb, st));
-    DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, loss, st));
+    DP_CHECK_HIP(launch_denoise(da, &nb, c.st));
+    DP_CHECK_HIP(launch_sum_partials(c.w.loss_part, nb, loss, c.st));
     return DPOSER_OK;
 }
 extern "C" int dposer_prior_loss(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                  const float* x0, const float* z, float t, int32_t weighted, float inv_n, float* x0_hat, float* grad,
                                  float* loss, uint64_t seed, uint32_t step, const float* freq, const float* sigmas, int64_t B,
                                  void* stream) {
-    DP_RANGE();
-    return prior_loss_impl(h, flat, packed_, ws_, sde, x0, z, t, weighted, inv_n, x0_hat, grad, loss, seed, step, freq, sigmas, B, stream, 0, 0);
+    return prior_loss_impl(__func__, h, flat, packed_, ws_, sde, x0, z, t, weighted, inv_n, x0_hat, grad, loss, seed, step, freq, sigmas, B, stream, 0, 0);
+}
+static int prior_table_impl(const char* entry, dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
+                            const float* t_host, int32_t n_rows, const float* freq, int64_t B, void* stream) {
+    SharedT c;
+    DP_TRY(c.check(entry, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG_AS(entry, t_host && freq && n_rows >= 1, "bad argument");
+    DP_CHECK_ARG_AS(entry, !sde || sde_kind_ok(sde), "unknown SDE kind");      // (null: dposer_prior_table_build, labels t * 999)
+    c.open(sde, DPOSER_WS_SHARED_T, n_rows);
+    return c.table(t_host, n_rows, freq);
 }
 extern "C" int dposer_prior_table_build(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const float* t_host,
                                         int32_t n_rows, const float* freq, int64_t B, void* stream) {
-    return dposer_prior_table_build_sde(h, flat, packed_, ws_, nullptr, t_host, n_rows, freq, B, stream);
+    return prior_table_impl(__func__, h, flat, packed_, ws_, nullptr, t_host, n_rows, freq, B, stream);
 }
 extern "C" int dposer_prior_table_build_sde(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                             const float* t_host, int32_t n_rows, const float* freq, int64_t B, void* stream) {
-    DP_RANGE();
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    DP_CHECK_ARG(t_host && freq && n_rows >= 1, "bad argument");
-    DP_CHECK_ARG(!sde || sde_kind_ok(sde), "unknown SDE kind");
-    hipStream_t st = (hipStream_t)stream;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, n_rows, (char*)ws_, w);
-    DP_TRY(stage_step_labels(h, w, sde, t_host, n_rows, st));      // labels = t * 999 (utils.py:152); VE: sigma(t)
-    return build_time_table(h, flat, (const char*)packed_, w, w.tt_labels, 0.f, n_rows, freq, st);
+    return prior_table_impl(__func__, h, flat, packed_, ws_, sde, t_host, n_rows, freq, B, stream);
 }
 extern "C" int dposer_prior_loss_tabled(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                         const float* x0, const float* z, float t, int32_t row, int32_t table_rows, int32_t weighted,
                                         float inv_n, float* x0_hat, float* grad, float* loss, uint64_t seed, uint32_t step,
                                         const float* sigmas, int64_t B, void* stream) {
-    DP_RANGE();
     DP_CHECK_ARG(table_rows >= 1, "table_rows must be >= 1");
-    return prior_loss_impl(h, flat, packed_, ws_, sde, x0, z, t, weighted, inv_n, x0_hat, grad, loss, seed, step, nullptr, sigmas, B, stream, row,
-                           table_rows);
+    return prior_loss_impl(__func__, h, flat, packed_, ws_, sde, x0, z, t, weighted, inv_n, x0_hat, grad, loss, seed, step, nullptr, sigmas, B, stream,
+                           row, table_rows);
 }
 
 // The prior loss on the MULTI-STEP estimate (multi_denoise = True: run/completion.py:112-149, smplify.py:76-107, motion_denoising.py:106-143):
@@ -1280,36 +1320,27 @@ extern "C" int dposer_prior_loss_multi(dposer_scorefc_t h, const float* flat, co
                                        const float* x0, const float* z, const float* t_traj_host, int32_t n_steps, int32_t weighted,
                                        float inv_n, float* x0_hat, float* grad, float* loss, uint64_t seed, uint32_t step, const float* freq,
                                        const float* sigmas, int64_t B, void* stream) {
-    DP_RANGE();
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
     DP_CHECK_ARG(n_steps >= 1 && n_steps <= 64, "n_steps must be in 1..64");
     DP_CHECK_ARG(t_traj_host, "t_traj_host is null (n_steps + 1 host floats)");
     DP_CHECK_ARG(sde && x0 && loss && freq && sigmas, "null argument");
     DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
     DP_CHECK_ARG(sde_kind_continuous(sde), "continuous score functions only (sub-VP, VP, VE): the discrete kinds are not verified for this entry");
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, n_steps, (char*)ws_, w);
-    DP_TRY(stage_step_labels(h, w, sde, t_traj_host, n_steps, st));      // the network is evaluated at time_traj[0 .. n_steps - 1]
-    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_steps, freq, st));
-    const SdeCfg sc = to_sde(sde);
-    PerturbSharedArgs pa;
-    pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t_traj_host[0]; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
-    pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
-    DP_CHECK_HIP(launch_perturb_shared(pa, st));
-    DdimStepArgs da;
-    da.res = w.res; da.xt = w.xt; da.xin = w.xin; da.sigmas = sigmas; da.x0 = x0; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = w.loss_part;
-    da.t0 = t_traj_host[0]; da.inv_n = inv_n; da.weighted = weighted; da.B = B; da.Bpad = w.Bpad; da.D = h->D; da.Dpad = h->Dpad; da.Cp = h->Cp;
-    da.num_scales = h->d.num_scales; da.scale_by_sigma = sbs_mode(h); da.f32 = h->f32; da.sde = sc;
+    c.open(sde, DPOSER_WS_SHARED_T, n_steps);
+    DP_TRY(c.table(t_traj_host, n_steps, freq));                         // the network is evaluated at time_traj[0 .. n_steps - 1]
+    DP_TRY(c.perturb(x0, z, t_traj_host[0], seed, step));
+    DdimStepArgs da{};
+    static_cast<ScoreOut&>(da) = score_out(c, sigmas, t_traj_host[0]);
+    da.xt = c.w.xt; da.xin = c.w.xin; da.x0 = x0; da.x0_hat = x0_hat; da.grad = grad; da.loss_part = c.w.loss_part;
+    da.t0 = t_traj_host[0]; da.inv_n = inv_n; da.weighted = weighted; da.Bpad = c.w.Bpad; da.f32 = c.h->f32;
     int nb = 0;
     for (int i = 0; i < n_steps; ++i) {
-        DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
+        DP_TRY(c.eval(i));
         da.t = t_traj_host[i]; da.t_next = t_traj_host[i + 1]; da.last = i + 1 == n_steps;
-        DP_CHECK_HIP(launch_ddim_step(da, &nb, st));
+        DP_CHECK_HIP(launch_ddim_step(da, &nb, c.st));
     }
-    DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, loss, st));
+    DP_CHECK_HIP(launch_sum_partials(c.w.loss_part, nb, loss, c.st));
     return DPOSER_OK;
 }
 
@@ -1318,30 +1349,22 @@ extern "C" int dposer_prior_loss_multi(dposer_scorefc_t h, const float* flat, co
 extern "C" int dposer_prior_red_diff(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde,
                                      const float* x0, const float* z, float t, float inv_batch, float* eps_pred, float* grad, float* loss,
                                      uint64_t seed, uint32_t step, const float* freq, const float* sigmas, int64_t B, void* stream) {
-    DP_RANGE();
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
     DP_CHECK_ARG(sde && x0 && loss && freq && sigmas, "null argument");
     DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
     DP_CHECK_ARG(sde_kind_continuous(sde), "continuous score functions only (sub-VP, VP, VE): the discrete kinds are not verified for this entry");
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, 1, (char*)ws_, w);
-    DP_TRY(build_time_table_at(h, flat, packed, w, sde, t, freq, st));
-    const SdeCfg sc = to_sde(sde);
-    PerturbSharedArgs pa;
-    pa.x0 = x0; pa.z_in = z; pa.xin = w.xin; pa.xt = w.xt; pa.t = t; pa.B = B; pa.Bpad = w.Bpad; pa.D = h->D; pa.Dpad = h->Dpad;
-    pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step;
-    DP_CHECK_HIP(launch_perturb_shared(pa, st));
-    DP_TRY(run_shared_t(h, flat, packed, w, 0, B, st));
-    RedDiffArgs ra;
-    ra.res = w.res; ra.x0 = x0; ra.z_in = z; ra.sigmas = sigmas; ra.eps_pred = eps_pred; ra.grad = grad; ra.loss_part = w.loss_part;
-    ra.t = t; ra.inv_batch = inv_batch; ra.B = B; ra.D = h->D; ra.Cp = h->Cp; ra.num_scales = h->d.num_scales; ra.scale_by_sigma = sbs_mode(h);
-    ra.sde = sc; ra.seed = seed; ra.step = step;
+    c.open(sde, DPOSER_WS_SHARED_T, 1);
+    DP_TRY(c.table_at(t, freq));
+    DP_TRY(c.perturb(x0, z, t, seed, step));
+    DP_TRY(c.eval(0));
+    RedDiffArgs ra{};
+    static_cast<ScoreOut&>(ra) = score_out(c, sigmas, t);
+    ra.x0 = x0; ra.z_in = z; ra.eps_pred = eps_pred; ra.grad = grad; ra.loss_part = c.w.loss_part; ra.inv_batch = inv_batch;
+    ra.seed = seed; ra.step = step;
     int nb = 0;
-    DP_CHECK_HIP(launch_red_diff(ra, &nb, st));
-    DP_CHECK_HIP(launch_sum_partials(w.loss_part, nb, loss, st));
+    DP_CHECK_HIP(launch_red_diff(ra, &nb, c.st));
+    DP_CHECK_HIP(launch_sum_partials(c.w.loss_part, nb, loss, c.st));
     return DPOSER_OK;
 }
 
@@ -1354,35 +1377,25 @@ extern "C" int dposer_completion_optimize(dposer_scorefc_t h, const float* flat,
                                           const float* w_data_host, int32_t n_steps, double lr, double beta1, double beta2, double eps,
                                           const float* noise, uint64_t seed, uint32_t step0, const float* freq, const float* sigmas,
                                           int64_t B, void* stream) {
-    DP_RANGE();
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
-    g_alg_batch = B;
-    DP_CHECK_ARG(sde && x && observation && mask && adam_m && adam_v && t_host && weighted_host && w_prior_host && w_data_host && freq && sigmas,
-                 "null argument");
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG(sde && x && observation && mask && adam_m && adam_v && t_host && weighted_host && w_prior_host && w_data_host && freq && sigmas, "null argument");
     DP_CHECK_ARG(sde_kind_ok(sde), "unknown SDE kind");
     DP_CHECK_ARG(n_steps >= 0, "n_steps must be >= 0");
+    c.open(sde, DPOSER_WS_SHARED_T, n_steps);
     if (n_steps == 0) return DPOSER_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_SHARED_T, n_steps, (char*)ws_, w);
-    DP_TRY(stage_step_labels(h, w, sde, t_host, n_steps, st));      // labels = t * 999 (utils.py:152) / sigma(t) (VE, :173)
-    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_steps, freq, st));
-    const SdeCfg sc = to_sde(sde);
+    DP_TRY(c.table(t_host, n_steps, freq));
     const int64_t BD = B * h->D;
+    CompletionUpdateArgs ua{};
+    static_cast<ScoreOut&>(ua) = score_out(c, sigmas, 0.f);      // (t: per step)
+    ua.xt = c.w.xt; ua.obs = observation; ua.mask = mask; ua.x = x; ua.m = adam_m; ua.v = adam_v;
+    ua.inv_n = (float)(1.0 / ((double)B * (double)h->D));
     for (int i = 0; i < n_steps; ++i) {
-        PerturbSharedArgs pa;
-        pa.x0 = x; pa.z_in = noise ? noise + (int64_t)i * BD : nullptr; pa.xin = w.xin; pa.xt = w.xt; pa.t = t_host[i]; pa.B = B; pa.Bpad = w.Bpad;
-        pa.D = h->D; pa.Dpad = h->Dpad; pa.f32 = h->f32; pa.sde = sc; pa.seed = seed; pa.step = step0 + (uint32_t)i;
-        DP_CHECK_HIP(launch_perturb_shared(pa, st));
-        DP_TRY(run_shared_t(h, flat, packed, w, i, B, st));
-        CompletionUpdateArgs ua;
-        ua.res = w.res; ua.xt = w.xt; ua.obs = observation; ua.mask = mask; ua.sigmas = sigmas; ua.x = x; ua.m = adam_m; ua.v = adam_v;
-        ua.t = t_host[i]; ua.inv_n = (float)(1.0 / ((double)B * (double)h->D)); ua.w_prior = w_prior_host[i]; ua.w_data = w_data_host[i];
-        ua.weighted = weighted_host[i];
+        DP_TRY(c.perturb(x, noise ? noise + (int64_t)i * BD : nullptr, t_host[i], seed, step0 + (uint32_t)i));
+        DP_TRY(c.eval(i));
+        ua.t = t_host[i]; ua.w_prior = w_prior_host[i]; ua.w_data = w_data_host[i]; ua.weighted = weighted_host[i];
         ua.s = adam_scalars(lr, beta1, beta2, eps, i + 1);
-        ua.B = B; ua.D = h->D; ua.Dpad = h->Dpad; ua.Cp = h->Cp; ua.num_scales = h->d.num_scales; ua.scale_by_sigma = sbs_mode(h); ua.sde = sc;
-        DP_CHECK_HIP(launch_completion_update(ua, st));
+        DP_CHECK_HIP(launch_completion_update(ua, c.st));
     }
     return DPOSER_OK;
 }
@@ -2113,7 +2126,8 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
                                      const float* observation, const float* mask, const float* noise, uint64_t seed, float* traj,
                                      int32_t traj_stride, int32_t project, float grad_step, int32_t* nonfinite_step, const float* freq,
                                      const float* sigmas, int64_t B, void* stream) {
-    DP_TRY(check_common(h, flat, packed_, ws_, B));
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
     DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
     DP_CHECK_ARG(observation && mask, "observation and mask are required");
     DP_CHECK_ARG(nonfinite_step, "nonfinite_step is required");
@@ -2121,21 +2135,17 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
     DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
     DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
     DP_CHECK_ARG(project == 0 || project == 1, "project must be 0 (DPS) or 1 (MCG)");
-    DP_RANGE();                                      // (every argument check is above: a refused call opens no range and launches nothing)
-    g_alg_batch = B;
-    hipStream_t st = (hipStream_t)stream;
-    const char* packed = (const char*)packed_;
-    const int N = sde->N;
-    const int n_run = (n_steps < 0 || n_steps > N - start_step) ? N - start_step : n_steps;
+    const int n_run = steps_to_run(sde->N, start_step, n_steps);
+    c.open(sde, DPOSER_WS_GUIDED, n_run);
     if (n_run == 0) return DPOSER_OK;
-    Ws w;
-    layout_ws(h, B, DPOSER_WS_GUIDED, n_run, (char*)ws_, w);
-    DP_TRY(stage_step_labels(h, w, sde, timesteps_host + start_step, n_run, st));
-    DP_TRY(build_time_table(h, flat, packed, w, w.tt_labels, 0.f, n_run, freq, st));
+    Ws& w = c.w;
+    hipStream_t st = c.st;
+    const char* packed = c.packed;
+    DP_TRY(c.table(timesteps_host + start_step, n_run, freq));
     const int k_noise = project ? 2 : 1;
     const int64_t BD = B * h->D;
     GuidedArgs ga{};
-    static_cast<UpdateCommon&>(ga) = update_common(h, w, sde, sigmas, x, x_mean, seed, B);
+    static_cast<UpdateCommon&>(ga) = update_common(c, sigmas, x, x_mean, seed);
     ga.obs = observation; ga.mask = mask; ga.dres = w.dres; ga.part = w.loss_part; ga.norm_sq = w.scalar; ga.dx = w.zbuf;
     ga.nonfinite = nonfinite_step; ga.grad_step = grad_step; ga.project = project;
     DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
@@ -2144,7 +2154,7 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
         const float* nz = noise ? noise + (int64_t)i * k_noise * BD : nullptr;
         ga.t = timesteps_host[gi]; ga.step = (uint32_t)gi;
         ga.z_pred = nz; ga.z_imp = (nz && project) ? nz + BD : nullptr;
-        ga.traj = (traj && ((i + 1) % traj_stride == 0)) ? traj + (int64_t)((i + 1) / traj_stride - 1) * BD : nullptr;
+        ga.traj = traj_slot(traj, i, traj_stride, BD);
         DP_TRY(forward_core_guided(h, flat, packed, w, i, B, st));
         int nb = 0;
         DP_CHECK_HIP(launch_guided_resid(ga, &nb, st));

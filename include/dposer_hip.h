@@ -14,7 +14,10 @@
  *     kernels are only enqueued, never synchronised, no allocation happens inside a call;
  *   - scratch memory is caller-owned: query *_bytes(), allocate once (e.g. a torch uint8
  *     tensor), pass the pointer;
- *   - return value: 0 = ok, <0 = error (DPOSER_ERR_*), message via dposer_last_error().
+ *   - return value: 0 = ok, <0 = error (DPOSER_ERR_*), message via dposer_last_error().  The entries that evaluate the network at one
+ *     time shared by the batch (the samplers, dposer_langevin_step, the dposer_prior_* family, dposer_completion_optimize) check every
+ *     argument before anything else: a refused call launches nothing and opens no roctx range, and its message starts with the name
+ *     of the entry that was called.
  */
 #ifndef DPOSER_HIP_H
 #define DPOSER_HIP_H
