@@ -1,7 +1,8 @@
 // The arithmetic the fitting loops share (completion, motion denoising, SMPLify, the training step): torch.optim.Adam's element update
 // with its host scalars, and the pose normaliser with its transpose, per coordinate and per joint.  Every user builds with
 // -ffp-contract=off: the expressions below are torch's unfused fp32 operations term for term, and their bits are held by the float64
-// oracles under tests/.
+// oracles under tests/: the fitting loops by oracle/task_loops.py, the training step's optimizer (k_adam_ema, k_adam_pack) by
+// tests/adam_ref.py.
 #pragma once
 #include <hip/hip_runtime.h>
 

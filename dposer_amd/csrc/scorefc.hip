@@ -2168,10 +2168,20 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
 extern "C" int dposer_grad_sqnorm(const float* grad, int64_t n, float* scratch, void* stream) {
     DP_RANGE();
     DP_CHECK_ARG(grad && scratch && n >= 0, "bad argument");
+    DP_CHECK_ARG(((uintptr_t)grad & 15) == 0, "grad must be 16-byte aligned (k_sqnorm reads it as float4)");
     hipStream_t st = (hipStream_t)stream;
     int nb = 0;
     DP_CHECK_HIP(launch_sqnorm(grad, n, scratch + 16, &nb, st));
     DP_CHECK_HIP(launch_sum_partials(scratch + 16, nb, scratch, st));
+    return DPOSER_OK;
+}
+// the no-gradient ranges of an optimizer call over n elements: at most two, each 0 <= lo <= hi <= n (a range outside the buffer means nothing)
+static int check_skip_ranges(const char* entry, const int64_t* skip_lo_host, const int64_t* skip_hi_host, int32_t n_skip, int64_t n) {
+    DP_CHECK_ARG_AS(entry, n_skip >= 0 && n_skip <= 2, "at most two no-gradient ranges");
+    DP_CHECK_ARG_AS(entry, n_skip == 0 || (skip_lo_host && skip_hi_host), "null argument");
+    for (int i = 0; i < n_skip; ++i)
+        DP_CHECK_ARG_AS(entry, 0 <= skip_lo_host[i] && skip_lo_host[i] <= skip_hi_host[i] && skip_hi_host[i] <= n,
+                        "a no-gradient range must satisfy 0 <= lo <= hi <= n");
     return DPOSER_OK;
 }
 // the optimizer kernels' argument block (every field): nb = number of k_sqnorm partials in scratch + 16, 0 = the sum is in scratch[0] already
@@ -2189,14 +2199,14 @@ static void fill_adam_args(AdamArgs& a, float* flat, const float* grad, float* m
 static int adam_step_impl(float* flat, const float* grad, float* m, float* v, float* ema, int64_t n, const int64_t* skip_lo_host,
                           const int64_t* skip_hi_host, int32_t n_skip, double lr, double beta1, double beta2, double eps, double grad_clip,
                           double grad_scale, int64_t adam_step, double ema_one_minus_decay, float* scratch, bool presummed, void* stream,
-                          double weight_decay);
+                          double weight_decay, const char* entry);
 extern "C" int dposer_adam_ema_clip_step(float* flat, const float* grad, float* m, float* v, float* ema, int64_t n,
                                          const int64_t* skip_lo_host, const int64_t* skip_hi_host, int32_t n_skip, double lr,
                                          double beta1, double beta2, double eps, double grad_clip, double grad_scale,
                                          int64_t adam_step, double ema_one_minus_decay, float* scratch, void* stream) {
     DP_RANGE();
     return adam_step_impl(flat, grad, m, v, ema, n, skip_lo_host, skip_hi_host, n_skip, lr, beta1, beta2, eps, grad_clip, grad_scale, adam_step,
-                          ema_one_minus_decay, scratch, false, stream, 0.0);
+                          ema_one_minus_decay, scratch, false, stream, 0.0, __func__);
 }
 extern "C" int dposer_adam_ema_clip_step_wd(float* flat, const float* grad, float* m, float* v, float* ema, int64_t n,
                                             const int64_t* skip_lo_host, const int64_t* skip_hi_host, int32_t n_skip, double lr,
@@ -2204,7 +2214,7 @@ extern "C" int dposer_adam_ema_clip_step_wd(float* flat, const float* grad, floa
                                             int64_t adam_step, double ema_one_minus_decay, float* scratch, int32_t presummed, void* stream) {
     DP_RANGE();
     return adam_step_impl(flat, grad, m, v, ema, n, skip_lo_host, skip_hi_host, n_skip, lr, beta1, beta2, eps, grad_clip, grad_scale, adam_step,
-                          ema_one_minus_decay, scratch, presummed != 0, stream, weight_decay);
+                          ema_one_minus_decay, scratch, presummed != 0, stream, weight_decay, __func__);
 }
 extern "C" int dposer_adam_ema_clip_step_presummed(float* flat, const float* grad, float* m, float* v, float* ema, int64_t n,
                                                    const int64_t* skip_lo_host, const int64_t* skip_hi_host, int32_t n_skip, double lr,
@@ -2212,15 +2222,17 @@ extern "C" int dposer_adam_ema_clip_step_presummed(float* flat, const float* gra
                                                    int64_t adam_step, double ema_one_minus_decay, float* scratch, void* stream) {
     DP_RANGE();
     return adam_step_impl(flat, grad, m, v, ema, n, skip_lo_host, skip_hi_host, n_skip, lr, beta1, beta2, eps, grad_clip, grad_scale, adam_step,
-                          ema_one_minus_decay, scratch, true, stream, 0.0);
+                          ema_one_minus_decay, scratch, true, stream, 0.0, __func__);
 }
 static int adam_step_impl(float* flat, const float* grad, float* m, float* v, float* ema, int64_t n, const int64_t* skip_lo_host,
                           const int64_t* skip_hi_host, int32_t n_skip, double lr, double beta1, double beta2, double eps, double grad_clip,
                           double grad_scale, int64_t adam_step, double ema_one_minus_decay, float* scratch, bool presummed, void* stream,
-                          double weight_decay) {
-    DP_CHECK_ARG(flat && grad && m && v && scratch, "null argument");
-    DP_CHECK_ARG(adam_step >= 1, "adam_step counts from 1");
-    DP_CHECK_ARG(n_skip >= 0 && n_skip <= 2, "at most two no-gradient ranges");
+                          double weight_decay, const char* entry) {
+    DP_CHECK_ARG_AS(entry, flat && grad && m && v && scratch, "null argument");
+    DP_CHECK_ARG_AS(entry, n >= 0, "n must be >= 0");
+    DP_CHECK_ARG_AS(entry, adam_step >= 1, "adam_step counts from 1");
+    DP_TRY(check_skip_ranges(entry, skip_lo_host, skip_hi_host, n_skip, n));
+    DP_CHECK_ARG_AS(entry, ((uintptr_t)grad & 15) == 0, "grad must be 16-byte aligned (k_sqnorm reads it as float4)");
     hipStream_t st = (hipStream_t)stream;
     int nb = 0;
     if (!presummed) DP_CHECK_HIP(launch_sqnorm(grad, n, scratch + 16, &nb, st));     // (the partials are added up by k_adam_ema)
@@ -2245,7 +2257,7 @@ extern "C" int dposer_scorefc_adam_pack_step(dposer_scorefc_t h, float* flat, co
     DP_CHECK_ARG(h && flat && grad && m && v && packed && scratch, "null argument");
     DP_CHECK_ARG(h->adam_pack.n_tensors > 0, "fused optimizer + re-pack step not available for this configuration");
     DP_CHECK_ARG(adam_step >= 1, "adam_step counts from 1");
-    DP_CHECK_ARG(n_skip >= 0 && n_skip <= 2, "at most two no-gradient ranges");
+    DP_TRY(check_skip_ranges(__func__, skip_lo_host, skip_hi_host, n_skip, h->nparams));
     DP_CHECK_ARG(((uintptr_t)flat & 15) == 0 && ((uintptr_t)grad & 15) == 0 && ((uintptr_t)m & 15) == 0 && ((uintptr_t)v & 15) == 0 &&
                      (!ema || ((uintptr_t)ema & 15) == 0) && ((uintptr_t)packed & 255) == 0, "buffers must be 16-byte aligned (packed: 256)");
     hipStream_t st = (hipStream_t)stream;

@@ -292,7 +292,9 @@ int dposer_scorefc_backward(dposer_scorefc_t h, const float* flat_params, const 
  *   AFTER this update (>= 1);  ema may be NULL;  ema_one_minus_decay = 1 - min(decay, (1+n)/(10+n));
  *   scratch: >= 8 KiB floats, caller-owned and persistent across steps: scratch[0] = squared gradient norm of this step,
  *   scratch[1] = number of steps DROPPED so far because that norm was not finite (NaN / Inf gradient: parameters, moments and
- *   EMA are left untouched on the device, no host round trip; zero scratch[1] once, before the first step). */
+ *   EMA are left untouched on the device, no host round trip; zero scratch[1] once, before the first step).
+ *   Refused (DPOSER_ERR_BAD_ARG): n < 0, a no-gradient range outside 0 <= lo <= hi <= n, flat_grad not 16-byte aligned (the norm
+ *   reads it four floats at a time; the other buffers need only float alignment). */
 int dposer_adam_ema_clip_step(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* ema,
                               int64_t n, const int64_t* skip_lo_host, const int64_t* skip_hi_host, int32_t n_skip,
                               double lr, double beta1, double beta2, double eps, double grad_clip, double grad_scale,
@@ -302,7 +304,8 @@ int dposer_adam_ema_clip_step(float* flat_params, const float* flat_grad, float*
  *   dposer_grad_sqnorm: scratch[0] = sum of squares of grad[0..n) (this rank's reduce-scattered gradient range); the caller
  *   all-reduces that one float over the ranks to get the global squared norm for clip_grad_norm_ (losses.py:54-55);
  *   dposer_adam_ema_clip_step_presummed: dposer_adam_ema_clip_step on the range, taking the squared norm from scratch[0] instead
- *   of recomputing it (pointers and skip ranges are relative to the range). */
+ *   of recomputing it (pointers and skip ranges are relative to the range).  grad must be 16-byte aligned in both: start every
+ *   range at a multiple of 4 floats. */
 int dposer_grad_sqnorm(const float* grad, int64_t n, float* scratch, void* stream);
 
 /* Runge-Kutta stage combination on the float64 state of the probability-flow ODE (lib/algorithms/advanced/likelihood.py:86-99,
