@@ -184,6 +184,13 @@ class BatchGatherArgs(C.Structure):
                 ("aux_out", C.c_void_p), ("indices", C.c_void_p)]
 
 
+class SetDistArgs(C.Structure):
+    """dposer_set_dist_args (include/dposer_hip.h), field for field."""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("na", C.c_int64), ("nb", C.c_int64), ("joints", C.c_int32), ("same_set", C.c_int32),
+                ("k", C.c_int32), ("radii", C.c_void_p), ("sum", C.c_void_p), ("knn_dist", C.c_void_p), ("knn_idx", C.c_void_p),
+                ("covered", C.c_void_p), ("splits", C.c_int32), ("scratch", C.c_void_p)]
+
+
 class DPoserHipError(RuntimeError):
     pass
 
@@ -251,6 +258,9 @@ SIGNATURES = {
     "dposer_draw_skeletons": (C.c_int, [C.POINTER(DrawSkeletonsArgs), vp]),
     "dposer_compose_panels": (C.c_int, [C.POINTER(ComposeArgs), vp]),
     "dposer_batch_gather": (C.c_int, [C.POINTER(BatchGatherArgs), vp]),
+    "dposer_pose_set_distances_scratch_bytes": (i64, [i64, i64, i32, i32, i32]),
+    "dposer_pose_set_distances_plan": (C.c_int, [i64, i64, i32, i32, C.POINTER(i32)]),
+    "dposer_pose_set_distances": (C.c_int, [C.POINTER(SetDistArgs), vp]),
     "dposer_dsm_loss_fwd_bwd": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,
                                           vp, vp, i64, vp]),
     "dposer_dsm_loss_fwd_bwd_bucketed": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, f32, u64, u32, vp, vp,

@@ -23,7 +23,7 @@ from ..algorithms.advanced.model import ScoreModelFC, TimeMLPs
 from ..algorithms.ema import ExponentialMovingAverage
 from ..dataset.AMASS import N_POSES, Evaler
 from ..dataset.feed import DeviceFeed
-from ..utils.metric import average_pairwise_distance
+from ..utils.metric import average_pairwise_distance, generation_fidelity
 from ..utils.misc import create_mask
 
 # the canvas and camera of the validation renders (train.py:46-48)
@@ -72,12 +72,15 @@ def _to_axis(config, x):
 
 
 def validate(state, sde, config, test_poses, body_model, denormalize, out_dir=None, *, render=False, log=None, device=None,
-             fused_eval=False):
+             fused_eval=False, fidelity_k=0):
     """The validation block of train.py:263-372 under the EMA weights: per test batch of ``config.eval.batch_size`` poses the bpd
     (likelihood ODE, rtol = atol = eps = 1e-4), five sampler completions of the left leg scored by ``Evaler.multi_eval_bodys`` and one
     generation; then APD over the first 22 joints of the first 50 samples and ``last_samples.npz`` (``pose_trajs [10, 5, D_axis]``,
     ``pose_samples [1, 50, D_axis]``) in ``out_dir``.  ``render=True`` adds the OBJ / image files of :338-362.  The model's parameters
-    are restored and it is left in train mode.  ``fused_eval`` scores the completions with ``Evaler.multi_eval_bodys(fused=True)``.  Returns ``{'bpd', 'mpvpe_all', 'mpjpe_body', 'APD'}`` as floats."""
+    are restored and it is left in train mode.  ``fused_eval`` scores the completions with ``Evaler.multi_eval_bodys(fused=True)``.  Returns ``{'bpd', 'mpvpe_all', 'mpjpe_body', 'APD'}`` as floats.
+    ``fidelity_k > 0`` adds the entries of ``utils.metric.generation_fidelity`` (``dNN``, ``precision``, ``recall``, ``density``,
+    ``coverage`` at that k, and its ``APD`` as ``APD_all``), computed from ALL generated samples -- not the 50 kept for the dump -- against
+    the first 22 joints of the test poses the batches covered."""
     model, ema = state["model"], state["ema"]
     device = torch.device(device) if device is not None else next(model.parameters()).device
     log = log or (lambda msg: None)
@@ -118,7 +121,13 @@ def validate(state, sde, config, test_poses, body_model, denormalize, out_dir=No
                 f"mpvpe_all {float(metrics['mpvpe_all'][-1]):.4f}, mpjpe_body {float(metrics['mpjpe_body'][-1]):.4f}")
         with torch.no_grad():
             trajs = trajs[::max(sde.N // 10, 1), :5]                                       # [10 times, 5 samples, D]
-            all_results = torch.cat(all_results, dim=0)[:50]
+            all_results = torch.cat(all_results, dim=0)
+            fidelity = {}
+            if fidelity_k > 0:
+                to_joints = lambda x: body_model(pose_body=_to_axis(config, denormalize(x)).reshape(-1, N_POSES * 3)).Jtr[:, :22, :].contiguous()
+                fid = generation_fidelity(to_joints(all_results), to_joints(test_poses[:n_batches * bs]), k=int(fidelity_k))
+                fidelity = {("APD_all" if key == "APD" else key): float(v) for key, v in fid.items()}
+            all_results = all_results[:50]
             trajs = _to_axis(config, denormalize(trajs)).reshape(-1, N_POSES * 3)
             all_results = _to_axis(config, denormalize(all_results)).reshape(-1, N_POSES * 3)
             joints = body_model(pose_body=all_results).Jtr[:, :22, :]
@@ -129,6 +138,7 @@ def validate(state, sde, config, test_poses, body_model, denormalize, out_dir=No
         model.train()
     out = {k: float(torch.stack(v).mean()) for k, v in metrics.items()}
     out["APD"] = apd
+    out.update(fidelity)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         np.savez(os.path.join(out_dir, "last_samples.npz"), pose_trajs=trajs.cpu().numpy().reshape(10, 5, -1),

@@ -6,7 +6,10 @@ live on, chunked so the [chunk, B, J] intermediate stays bounded.
 
 ``self_intersecting_faces`` / ``self_intersections_percentage_hip`` are the SI metric computed by this package's own kernels
 (csrc/meshsi.hip, pair rule in include/dposer_hip.h); ``self_intersections_percentage`` stays the reference's PyMeshLab path.
-``generation_metrics`` is the APD + SI pair of demo.py:148-161."""
+``generation_metrics`` is the APD + SI pair of demo.py:148-161.
+
+``pose_set_distances`` and what is built on it (``average_pairwise_distance_hip``, ``nearest_pose_distance``, ``generation_fidelity``) reduce
+over the matrix of APD distances between two pose sets without storing it (csrc/setdist.hip, rules in include/dposer_hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -23,6 +26,127 @@ def average_pairwise_distance(joints3d, chunk=1024):
         d = torch.linalg.norm(x[lo:lo + chunk, None] - x[None], dim=-1).mean(dim=-1)      # [c, B]; the diagonal is exactly 0
         total += d.double().sum()
     return (total / (B * (B - 1))).float()
+
+
+MAX_NEIGHBOURS, MAX_SET_JOINTS = 8, 128          # limits of dposer_pose_set_distances
+
+
+def _pose_set(x, name):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[-1] != 3:
+        raise ValueError(f"{name} must be a tensor [N, J, 3], got {tuple(x.shape) if hasattr(x, 'shape') else type(x).__name__}")
+    if x.shape[0] < 1 or not 1 <= x.shape[1] <= MAX_SET_JOINTS:
+        raise ValueError(f"{name} needs N >= 1 poses of 1 <= J <= {MAX_SET_JOINTS} joints, got {tuple(x.shape)}")
+    return x
+
+
+def pose_set_distances(a, b=None, *, k=0, radii=None, want_sum=False, splits=0):
+    """Reductions over the distances d(a_i, b_j) = mean over joints of ||a_i - b_j|| of two pose sets ``a [na, J, 3]`` and ``b [nb, J, 3]`` on a ROCm
+    device (``dposer_pose_set_distances``; the rules are written out in include/dposer_hip.h).  ``b=None``: the set against itself, each
+    row's own index left out of the neighbour and covered outputs.  Returns a dict of device tensors with, as asked for,
+    ``"knn_dist" float32 [na, k]`` / ``"knn_idx" int32 [na, k]`` (``1 <= k <= 8``: the k nearest, ascending, ties to the smaller index, tail
+    ``+inf`` / ``-1``), ``"covered" int32 [na]`` (``radii float [nb]`` given: the count of j with d(a_i, b_j) <= radii[j]) and ``"sum"
+    float64 []`` (``want_sum``: the sum of all distances).  ``splits``: 0 = the library's choice; the outputs do not depend on it beyond the
+    last bits of ``sum``.  Never synchronises with the host."""
+    from .. import _C
+    a = _pose_set(a, "a")
+    same = b is None
+    if not same:
+        b = _pose_set(b, "b")
+        if b.shape[1] != a.shape[1]:
+            raise ValueError(f"a and b must have the same joint count, got {a.shape[1]} and {b.shape[1]}")
+    na, J = int(a.shape[0]), int(a.shape[1])
+    nb = na if same else int(b.shape[0])
+    k, splits = int(k), int(splits)
+    if not 0 <= k <= MAX_NEIGHBOURS:
+        raise ValueError(f"k must lie in [0, {MAX_NEIGHBOURS}], got {k}")
+    if splits < 0:
+        raise ValueError(f"splits must be >= 0, got {splits}")
+    if nb >= 2 ** 31:
+        raise ValueError("reference sets of 2^31 poses and more are not supported")
+    if radii is not None and (not isinstance(radii, torch.Tensor) or tuple(radii.shape) != (nb,)):
+        raise ValueError(f"radii must be a tensor [{nb}], got {tuple(radii.shape) if hasattr(radii, 'shape') else type(radii).__name__}")
+    if k == 0 and radii is None and not want_sum:
+        raise ValueError("nothing asked for: give k >= 1, radii or want_sum=True")
+    _C.require_gpu(a, "a")
+    if not same:
+        _C.require_gpu(b, "b")
+    if radii is not None:
+        _C.require_gpu(radii, "radii")
+    dev = a.device
+    a = a.detach().to(torch.float32).contiguous()
+    b = None if same else b.detach().to(device=dev, dtype=torch.float32).contiguous()
+    radii = None if radii is None else radii.detach().to(device=dev, dtype=torch.float32).contiguous()
+    out = {}
+    if k > 0:
+        out["knn_dist"] = torch.empty((na, k), dtype=torch.float32, device=dev)
+        out["knn_idx"] = torch.empty((na, k), dtype=torch.int32, device=dev)
+    if radii is not None:
+        out["covered"] = torch.empty((na,), dtype=torch.int32, device=dev)
+    if want_sum:
+        out["sum"] = torch.empty((), dtype=torch.float64, device=dev)
+    lib = _C.lib()
+    nbytes = int(lib.dposer_pose_set_distances_scratch_bytes(na, nb, J, k, splits))
+    if nbytes < 0:
+        _C.check(nbytes, "dposer_pose_set_distances_scratch_bytes")
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    args = _C.SetDistArgs(a=a.data_ptr(), b=None if same else b.data_ptr(), na=na, nb=nb, joints=J, same_set=1 if same else 0, k=k,
+                          radii=None if radii is None else radii.data_ptr(), sum=out["sum"].data_ptr() if want_sum else None,
+                          knn_dist=out["knn_dist"].data_ptr() if k > 0 else None, knn_idx=out["knn_idx"].data_ptr() if k > 0 else None,
+                          covered=out["covered"].data_ptr() if radii is not None else None, splits=splits, scratch=scratch.data_ptr())
+    with torch.cuda.device(dev):
+        _C.check(lib.dposer_pose_set_distances(C.byref(args), _C.stream_ptr()), "dposer_pose_set_distances")
+    return out
+
+
+def average_pairwise_distance_hip(joints3d):
+    """APD of ``joints3d [B, J, 3]`` as a device scalar (float32), the quantity of ``average_pairwise_distance`` without its
+    ``[chunk, B, J, 3]`` intermediate: one ``pose_set_distances`` call in its symmetric form."""
+    B = int(joints3d.shape[0]) if hasattr(joints3d, "shape") and len(joints3d.shape) else 0
+    if B < 2:
+        raise ValueError("APD needs at least two poses")
+    total = pose_set_distances(joints3d, want_sum=True)["sum"]
+    return (total / (B * (B - 1))).float()
+
+
+def nearest_pose_distance(query, reference, k=1):
+    """``(dist float32 [N, k], idx int32 [N, k])``: the ``k`` nearest poses of ``reference [M, J, 3]`` to each pose of ``query [N, J, 3]``
+    under the APD distance, ascending (the memorisation / novelty check of a generated set against the training set)."""
+    if int(k) < 1:
+        raise ValueError(f"k must be >= 1, got {k}")
+    out = pose_set_distances(query, reference, k=k)
+    return out["knn_dist"], out["knn_idx"]
+
+
+def generation_fidelity(gen_joints, real_joints, k=3):
+    """Fidelity scores of generated poses ``G = gen_joints [N, J, 3]`` against real ones ``R = real_joints [M, J, 3]`` under the APD
+    distance, as device scalars: ``{"APD", "dNN", "precision", "recall", "density", "coverage"}``.
+
+    With r_R[i] the distance of R_i to its k-th nearest neighbour inside R (itself excluded) and r_G[n] the same inside G:
+    ``precision`` = mean_n 1[exists i: d(G_n, R_i) <= r_R[i]] and ``recall`` = mean_i 1[exists n: d(R_i, G_n) <= r_G[n]] (improved
+    precision / recall, Kynkaanniemi et al. 2019); ``density`` = sum_n #{i: d(G_n, R_i) <= r_R[i]} / (k N) and ``coverage`` =
+    mean_i 1[min_n d(R_i, G_n) <= r_R[i]] (Naeem et al. 2020); ``dNN`` = mean_n min_i d(G_n, R_i); ``APD`` of G.  Five library calls:
+    the radii of R and of G, G against R (covered + nearest), R against G (covered + nearest), and the APD sum.  Needs N, M >= k + 1."""
+    gen_joints, real_joints = _pose_set(gen_joints, "gen_joints"), _pose_set(real_joints, "real_joints")
+    k = int(k)
+    if not 1 <= k <= MAX_NEIGHBOURS:
+        raise ValueError(f"k must lie in [1, {MAX_NEIGHBOURS}], got {k}")
+    if gen_joints.shape[1] != real_joints.shape[1]:
+        raise ValueError(f"both sets must have the same joint count, got {gen_joints.shape[1]} and {real_joints.shape[1]}")
+    N, M = int(gen_joints.shape[0]), int(real_joints.shape[0])
+    if N < k + 1 or M < k + 1:
+        raise ValueError(f"generation_fidelity with k = {k} needs at least {k + 1} poses in each set, got {N} and {M}")
+    r_real = pose_set_distances(real_joints, k=k)["knn_dist"][:, k - 1].contiguous()
+    r_gen = pose_set_distances(gen_joints, k=k)["knn_dist"][:, k - 1].contiguous()
+    g2r = pose_set_distances(gen_joints, real_joints, k=1, radii=r_real)
+    r2g = pose_set_distances(real_joints, gen_joints, k=1, radii=r_gen)
+    apd = average_pairwise_distance_hip(gen_joints)
+    cov_g, cov_r = g2r["covered"], r2g["covered"]
+    return {"APD": apd,
+            "dNN": g2r["knn_dist"][:, 0].double().mean().float(),
+            "precision": (cov_g > 0).double().mean().float(),
+            "recall": (cov_r > 0).double().mean().float(),
+            "density": (cov_g.double().sum() / (k * N)).float(),
+            "coverage": (r2g["knn_dist"][:, 0] <= r_real).double().mean().float()}
 
 
 def self_intersections_percentage(vertices, faces):

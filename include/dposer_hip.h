@@ -1209,6 +1209,57 @@ typedef struct dposer_batch_gather_args {
 } dposer_batch_gather_args;
 int dposer_batch_gather(const dposer_batch_gather_args* args, void* stream);
 
+/* All-pairs pose-set distances -- the sum, the k nearest references of every row and the count of references whose radius covers a row, over
+ * the matrix d(a_i, b_j) of two pose sets A [na, J, 3] and B [nb, J, 3] (fp32, contiguous), in one call and without storing the matrix.  APD,
+ * the nearest-neighbour distance to a reference set and the k-NN manifold scores (precision / recall, density / coverage) all reduce over it.
+ * Distance.  d(a, b) = (1 / J) sum_j ||a_j - b_j||, the distance of lib/utils/metric.py:8-37.  The differences are formed directly (never
+ *   |a|^2 + |b|^2 - 2 a.b, which cancels exactly where nearest neighbours live).  Per joint: dx = ax - bx, dy, dz; s = fma(dz, dz, fma(dy, dy,
+ *   dx dx)); one v_sqrt_f32 (1 ulp).  The joints are added in index order in fp32, starting from 0, then one multiply by the fp32 value of 1 / J.
+ *   A distance is a function of the two poses and J alone: not of k, the outputs asked for, the split or the pose's position in its set.
+ * Self exclusion.  same_set != 0: B is A (b = a or NULL, nb = na); column j == i is left out of the k-NN and covered outputs of row i.  Only
+ *   the index is excluded: another row equal to a_i is its neighbour at distance 0.
+ * Outputs, any subset (NULL = not wanted, at least one is wanted):
+ *   sum      double[1]: sum_i sum_j d(a_i, b_j), the diagonal of the same set included -- it is exactly 0, so APD = sum / (n (n - 1)).  A lane
+ *            adds the distances of at most 16 consecutive references of a tile in fp32, then in fp64: a row's tiles in order, the 64 rows of
+ *            a wave by xor butterfly, the four waves of a workgroup in order, the workgroups' sums (row block major, split minor) by 256
+ *            strided sums and the same tree.  With same_set and sum alone the tiles left of a row block's own 256 columns are skipped and the
+ *            tiles right of them count twice (d is symmetric bit for bit).  No atomics: the order depends on (na, nb, J, k, splits) and on
+ *            which outputs are asked for, and two calls on the same inputs return the same bits.
+ *   knn_dist float[na, k], knn_idx int32[na, k], 1 <= k <= 8: the k smallest distances of each row, ascending; equal distances in index
+ *            order; fewer than k candidates: the tail is +inf / -1.
+ *   covered  int32[na]: the count of j with d(a_i, b_j) <= radii[j]; radii float[nb] is required with it.
+ *   NaN: a NaN distance is never a neighbour and never covers; sum propagates it.  (A +inf distance is never a neighbour either.)
+ * Limits: 1 <= J <= 128, na >= 1, 1 <= nb < 2^31; na nb may pass 2^32.  Everything else is refused (DPOSER_ERR_BAD_ARG) before a launch.
+ * Plan.  Workgroups of plan[0] rows (one lane per row) stream tiles of plan[1] references through LDS; the references are cut into `splits`
+ *   ranges of whole tiles across the grid, and a second pass merges the partial k-lists, counts and sums in split order, so no output but the
+ *   last bits of sum depends on the split.  plan[2] is the split count the library chooses for splits = 0; splits > 0 forces that many, up to
+ *   one per tile and at most 64.  plan[3] = 1: J = 22 rows are kept in registers; 0: the general path (both sets pass through LDS in chunks
+ *   of 8 joints).  dposer_pose_set_distances_plan is a pure function of its arguments.
+ * scratch: dposer_pose_set_distances_scratch_bytes(na, nb, joints, k, splits) bytes (< 0: refused), 256-byte aligned.  Queues up to three
+ *   kernels on the stream; allocates nothing, never synchronises the host.
+ * Cost note: a (pair, joint) is 3 v_sub + v_mul + 2 v_fma + v_sqrt_f32 + v_add = 7 x 4 + 8 = 36 issue cycles per wave, so the VALU issue floor
+ *   is 256 CUs x 4 SIMDs x 64 lanes / 36 cycles x clock = 3.6e12 pair-joints/s at 2 GHz (measured: profiles/set_dist_time.md).
+ * Layout (LP64): pointers and int64 at 8-byte alignment, int32 at 4; sizeof = 104. */
+typedef struct dposer_set_dist_args {
+    const float* a;                   /*   0: [na, joints, 3] */
+    const float* b;                   /*   8: [nb, joints, 3]; same_set: a or NULL */
+    int64_t na;                       /*  16 */
+    int64_t nb;                       /*  24 */
+    int32_t joints;                   /*  32 */
+    int32_t same_set;                 /*  36 */
+    int32_t k;                        /*  40 */
+    const float* radii;               /*  48: [nb] or NULL */
+    double* sum;                      /*  56: [1] or NULL */
+    float* knn_dist;                  /*  64: [na, k] or NULL */
+    int32_t* knn_idx;                 /*  72: [na, k] or NULL */
+    int32_t* covered;                 /*  80: [na] or NULL */
+    int32_t splits;                   /*  88: 0 = the library chooses */
+    void* scratch;                    /*  96 */
+} dposer_set_dist_args;
+int64_t dposer_pose_set_distances_scratch_bytes(int64_t na, int64_t nb, int32_t joints, int32_t k, int32_t splits);
+int dposer_pose_set_distances_plan(int64_t na, int64_t nb, int32_t joints, int32_t k, int32_t plan[4]);
+int dposer_pose_set_distances(const dposer_set_dist_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
