@@ -781,6 +781,166 @@ def get_guided_sampler(sde, shape, inverse_scaler, method, grad_step=1.0, contin
     return guided_sampler
 
 
+JOINT_GUIDED_NORMS = ("batch", "sample")
+
+
+def fused_joint_guided_supported(sde, model, continuous):
+    """What ``dposer_joint_guided_sampler`` takes: ``fused_guided_supported`` and a network on 21 axis-angle joints (63 inputs)."""
+    return bool(fused_guided_supported(sde, model, continuous)) and int(model.n_poses) * int(model.joint_dim) == 63
+
+
+def _joint_guided_problem(body_model, normalizer, joints3d, joints_conf, obs_joints, root_orient, trans, betas, B):
+    """Host checks of a 3D-joint observation for ``B`` poses (shapes, ``obs_joints`` range and distinctness -- before any device work),
+    then its device tensors: (obs [B, n_obs, 3], conf [B, n_obs] or None, rows list or None)."""
+    from ...tasks.motion_denoising import _partial_observation
+    if joints3d.dim() != 3 or tuple(joints3d.shape[::2]) != (B, 3) or not 1 <= joints3d.shape[1] <= 22:
+        raise ValueError(f"joints3d must be [{B}, 1..22, 3], got {list(joints3d.shape)}")
+    for name, t in (("root_orient", root_orient), ("trans", trans)):
+        if t is not None and tuple(t.shape) != (B, 3):
+            raise ValueError(f"{name} must be [{B}, 3], got {list(t.shape)}")
+    if betas is not None and (betas.dim() != 2 or betas.shape[0] != B):
+        raise ValueError(f"betas must be [{B}, n], got {list(betas.shape)}")
+    conf, rows = _partial_observation(joints3d, joints_conf, obs_joints, 22)
+    return joints3d, conf, rows
+
+
+def fused_joint_guided_sample(model, sde, x, timesteps, body_model, normalizer, joints3d, *, joints_conf=None, obs_rows=None, root_orient=None,
+                              trans=None, betas=None, norm="sample", grad_step=1.0, start_step=0, run_steps=-1, noise=None, seed=0, traj_stride=0,
+                              continuous=True):
+    """dposer_joint_guided_sampler: loop indices [start_step, start_step + run_steps) (run_steps < 0: to N) of DPS on observed 3D joints in
+    ONE library call, then one 4-byte read of the non-finite flag.  x [B, 63] initial state (consumed); ``joints3d`` [B, n_obs, 3],
+    ``joints_conf`` [B, n_obs] or None, ``obs_rows`` a list of n_obs distinct joints in [0, 22) or None -- already checked
+    (``get_joint_guided_sampler`` does).  Returns (trajs or None, x, x_mean)."""
+    from ...tasks._fused import normalizer_tables
+    N = int(sde.N)
+    n_run = N - start_step if (run_steps < 0 or run_steps > N - start_step) else int(run_steps)
+    _C.require_gpu(joints3d, "joint-guided sampler observation")
+    p = _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, None, None, noise, with_backward=True)
+    if p.B == 0:
+        return p.traj, p.x, p.x_mean
+    eng, B, dev = p.eng, p.B, x.device
+    core = body_model.bm
+    with torch.no_grad():
+        _, j_rest, batched = core.rest_shape(betas, None)
+    f32 = lambda t: None if t is None else t.detach().to(dev).contiguous().float()
+    obs, conf, root, tr, jr = f32(joints3d), f32(joints_conf), f32(root_orient), f32(trans), f32(j_rest)
+    mode, na, nb = normalizer_tables(normalizer, p.x)
+    rows_d = None if obs_rows is None else torch.tensor([int(r) for r in obs_rows], dtype=torch.int32, device=dev)
+    ws = eng.workspace(B, _C.WS_GUIDED, max(n_run, 1), dev)
+    scratch = torch.empty(eng.lib.dposer_joint_guided_scratch_bytes(B), dtype=torch.uint8, device=dev)
+    flag = torch.full((1,), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+    _C.check(eng.lib.dposer_joint_guided_sampler(eng.h, _C.ptr(p.flat), _C.ptr(p.packed), _C.ptr(ws), C.byref(p.desc), _C.ptr(p.x), _C.ptr(p.x_mean),
+                                                 C.c_void_p(p.ts_host.data_ptr()), int(start_step), int(run_steps), core._handle(), mode, _C.ptr(na),
+                                                 _C.ptr(nb), _C.ptr(root), _C.ptr(tr), _C.ptr(jr), 1 if batched else 0, _C.ptr(obs), _C.ptr(conf),
+                                                 _C.ptr(rows_d), int(obs.shape[1]), JOINT_GUIDED_NORMS.index(norm), _C.ptr(p.nz), int(seed),
+                                                 _C.ptr(p.traj), int(traj_stride or 1), float(grad_step), _C.ptr(flag), _C.ptr(scratch),
+                                                 _C.ptr(eng.freq(dev, model._fourier_W())), _C.ptr(model.sigmas), B, _C.stream_ptr()),
+             "dposer_joint_guided_sampler")
+    bad = int(flag.item())                           # the call's one host read, after the loop
+    if bad != 2 ** 31 - 1:
+        raise ValueError("Consider reduce the value of parameter: grad_step={} (the gradient is not finite at loop index {})".format(grad_step, bad))
+    return p.traj, p.x, p.x_mean
+
+
+def joint_guided_step(rsde, body_model, normalizer, x_t, t, z, obs, conf, rows, root_orient, trans, betas, norm, grad_step):
+    """One step of DPS on observed 3D joints with torch autograd through the score function and ``fk_joints(grad="chain")`` -- what
+    ``dposer_joint_guided_sampler`` runs per loop index, for the models and SDEs it does not take.  Returns (y_hat, y_mean)."""
+    import contextlib
+    x_t = x_t.detach().requires_grad_()
+    dt = -1.0 / rsde.N
+    model = getattr(getattr(rsde, "_score_fn", None), "model", None)
+    only_x = model.input_grad_only() if hasattr(model, "input_grad_only") else contextlib.nullcontext()
+    with torch.enable_grad():
+        with only_x:
+            drift, diffusion, alpha, sigma_2, score = rsde.sde(x_t, t, None, None, guide=True)
+        y_mean = x_t.detach() + drift.detach() * dt
+        y_hat = y_mean + diffusion[:, None] * np.sqrt(-dt) * z
+        y0 = (x_t + sigma_2[:, None] * score) / alpha
+        joints = body_model.fk_joints(normalizer.offline_denormalize(y0), root_orient=root_orient, trans=trans, betas=betas, grad="chain")
+        idx = torch.arange(obs.shape[1], device=obs.device) if rows is None else torch.tensor(rows, dtype=torch.long, device=obs.device)
+        c = torch.ones(obs.shape[:2], dtype=y0.dtype, device=obs.device) if conf is None else conf
+        live = c > 0                                 # false for 0, negatives and NaN; a dead entry never enters a sum
+        r = joints[:, idx] - torch.where(live[..., None], obs, torch.zeros_like(obs))
+        s = (torch.where(live, c, torch.zeros_like(c)) * (r * r).sum(dim=2)).sum(dim=1)
+        if norm == "batch":
+            s = s.sum().reshape(1)
+        on = s > 0                                   # norm == 0: no guidance (sqrt has no gradient there)
+        total = torch.where(on, torch.sqrt(torch.where(on, s, torch.ones_like(s))), torch.zeros_like(s)).sum()
+        g = torch.autograd.grad(total, x_t)[0] if total.requires_grad else torch.zeros_like(y_hat)
+    if not torch.isfinite(g).all() or not torch.isfinite(s).all():
+        raise ValueError("Consider reduce the value of parameter: grad_step={}".format(grad_step))
+    return (y_hat - grad_step * g).detach(), y_mean.detach()
+
+
+def get_joint_guided_sampler(sde, shape, body_model, normalizer, grad_step=1.0, norm="sample", continuous=True, denoise=True, eps=1e-3,
+                             device="cuda"):
+    """DPS on observed 3D joints: the loop of ``get_guided_sampler`` with the posed body joints as the measurement -- a head and two wrists
+    from a headset, a detector's joints with an occluded limb -- instead of a pose-space mask; several calls (or a tiled batch) draw
+    several plausible bodies for one observation.
+
+    ``sampler(model, joints3d, joints_conf=None, obs_joints=None, root_orient=None, trans=None, betas=None, z=None, start_step=0, *,
+    traj_stride=1, noise=None, seed=None)`` returns ``(trajs [n, B, 63], x_mean if denoise else x)`` in the network's normalised space.
+    ``joints3d`` [B, n_obs, 3]; ``joints_conf`` [B, n_obs] or [n_obs]: an entry counts iff its confidence is > 0 and what lies under a dead
+    entry may be NaN; ``obs_joints``: the n_obs distinct joints in [0, 22) the columns observe (default 0 .. n_obs - 1).  ``norm``:
+    "sample" -- every row is its own problem, guided by the gradient of its own residual norm -- or "batch", the reference's
+    ``torch.norm`` over the whole batch.  A row (or, under "batch", a batch) without a live entry is sampled unconditionally.  ``noise``
+    [n_run, 1, B, 63] injects the draws.  A ScoreModelFC on 63 inputs under continuous sub-VP / VP runs as ONE
+    ``dposer_joint_guided_sampler`` call; everything else steps ``joint_guided_step`` in Python."""
+    if norm not in JOINT_GUIDED_NORMS:
+        raise ValueError(f"unknown norm scope {norm!r}: expected one of {JOINT_GUIDED_NORMS}")
+    if len(shape) != 2 or int(shape[1]) != 63:
+        raise ValueError(f"the joint-guided sampler works on [B, 63] axis-angle body poses, got shape {tuple(shape)}")
+    call_count = [0]
+
+    def joint_guided_sampler(model, joints3d, joints_conf=None, obs_joints=None, root_orient=None, trans=None, betas=None, z=None, start_step=0, *,
+                             traj_stride=1, noise=None, seed=None):
+        B = int(shape[0])
+        obs, conf, rows = _joint_guided_problem(body_model, normalizer, joints3d, joints_conf, obs_joints, root_orient, trans, betas, B)
+        if z is not None and tuple(z.shape) != tuple(shape):
+            raise ValueError(f"z {tuple(z.shape)} does not have the sampler's shape {tuple(shape)}")
+        if not 0 <= start_step <= sde.N:
+            raise ValueError(f"start_step {start_step} outside [0, {sde.N}]")
+        n_run = sde.N - start_step
+        if noise is not None and tuple(noise.shape) != (n_run, 1) + tuple(shape):
+            raise ValueError(f"noise {tuple(noise.shape)}: expected {(n_run, 1) + tuple(shape)}")
+        x = sde.prior_sampling(shape).to(device) if z is None else z
+        _C.require_gpu(x, "sampler state")
+        _C.require_gpu(joints3d, "joint-guided sampler observation")
+        if fused_joint_guided_supported(sde, model, continuous):
+            call_count[0] += 1
+            if seed is None:
+                seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
+            was_training = model.training
+            model.eval()
+            try:
+                with torch.no_grad():
+                    trajs, x, x_mean = fused_joint_guided_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), body_model, normalizer, obs,
+                                                                 joints_conf=conf, obs_rows=rows, root_orient=root_orient, trans=trans, betas=betas,
+                                                                 norm=norm, grad_step=grad_step, start_step=start_step, noise=noise, seed=seed,
+                                                                 traj_stride=traj_stride, continuous=continuous)
+            finally:
+                model.train(was_training)
+            if trajs is None:
+                trajs = x.new_empty((0,) + tuple(x.shape))
+            return trajs, (x_mean if denoise else x)
+        score_fn = mutils.get_score_fn(sde, model, train=False, continuous=continuous)
+        rsde = sde.reverse(score_fn, False)
+        timesteps = torch.linspace(sde.T, eps, sde.N, device=x.device)
+        obs_d = obs.to(x.device).float()
+        conf_d = None if conf is None else conf.to(x.device).float()
+        trajs, x_mean = [], x
+        for i in range(start_step, sde.N):
+            vec_t = torch.ones(shape[0], device=x.device) * timesteps[i]
+            zi = torch.randn_like(x) if noise is None else noise[i - start_step, 0]
+            x, x_mean = joint_guided_step(rsde, body_model, normalizer, x, vec_t, zi, obs_d, conf_d, rows, root_orient, trans, betas, norm, grad_step)
+            if traj_stride and (i - start_step + 1) % traj_stride == 0:
+                trajs.append(x)
+        trajs = torch.stack(trajs, dim=0) if trajs else x.new_empty((0,) + tuple(x.shape))
+        return trajs, (x_mean if denoise else x)
+
+    return joint_guided_sampler
+
+
 def get_ode_sampler(sde, shape, inverse_scaler, denoise=False, rtol=1e-5, atol=1e-5, method="RK45", eps=1e-3, device="cuda", driver=None,
                     n_steps=None):
     """Probability-flow ODE sampler (sampling.py:471-542): ``ode_sampler(model, z=None) -> (nfe, samples)``.

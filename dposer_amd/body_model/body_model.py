@@ -164,6 +164,54 @@ class _LBSFunction(torch.autograd.Function):
         return (None, None, g_vs, g_jr, d_transl, *dsegs)
 
 
+class _FKJointsFunction(torch.autograd.Function):
+    """dposer_fk_joints / dposer_fk_joints_backward as one differentiable op: posed joints [B, n_out, 3] whose gradient is the chain
+    rule over those joints alone (no vertices, no skinning, no blend GEMM -- what ``_LBSFunction`` pays for the same numbers).
+    inputs: core, batched, j_rest, transl (or None), n_out, the pose segments in ``core.segments`` order (any may be None)."""
+
+    @staticmethod
+    def forward(ctx, core, batched, j_rest, transl, n_out, *segs):
+        B = next(t for t in segs if t is not None).shape[0] if any(t is not None for t in segs) else (transl.shape[0] if transl is not None else j_rest.shape[0])
+        dev = core.v_template.device
+        h, lib = core._handle(), _C.lib()
+        segp, segj, keep = _marshal_segments(core, segs, B)
+        jr = j_rest.detach().contiguous().float()
+        tr = None if transl is None else transl.detach().contiguous().float()
+        joints = torch.empty(B, n_out, 3, dtype=torch.float32, device=dev)
+        _C.check(lib.dposer_fk_joints(h, segp, segj, len(core.segments), _C.ptr(jr), 1 if batched else 0, _C.ptr(tr), _C.ptr(joints), None, n_out, B,
+                                      _C.stream_ptr()), "dposer_fk_joints")
+        ctx.core, ctx.batched, ctx.keep, ctx.jr, ctx.B, ctx.n_out = core, batched, keep, jr, B, n_out
+        ctx.has_transl = transl is not None
+        return joints
+
+    @staticmethod
+    def backward(ctx, d_joints):
+        core, B, n_out = ctx.core, ctx.B, ctx.n_out
+        dev = d_joints.device
+        h, lib = core._handle(), _C.lib()
+        dj = d_joints.contiguous().float()
+        d_transl = dj.sum(dim=1) if ctx.has_transl else None
+        segp, dsegp = (C.c_void_p * _MAX_SEG)(), (C.c_void_p * _MAX_SEG)()
+        segj = (C.c_int32 * _MAX_SEG)()
+        dsegs = []
+        for i, ((_, nj), t) in enumerate(zip(core.segments, ctx.keep)):
+            segj[i] = nj
+            segp[i] = None if t is None else t.data_ptr()
+            g = None if t is None or not ctx.needs_input_grad[5 + i] else torch.empty_like(t)
+            dsegs.append(g)
+            dsegp[i] = None if g is None else g.data_ptr()
+        d_jrest = torch.empty(B, n_out, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(lib.dposer_fk_joints_backward_workspace_bytes(h, n_out, B), dtype=torch.uint8, device=dev)
+        _C.check(lib.dposer_fk_joints_backward(h, segp, segj, len(core.segments), _C.ptr(ctx.jr), 1 if ctx.batched else 0, _C.ptr(dj), n_out * 3,
+                                               n_out, dsegp, _C.ptr(d_jrest), _C.ptr(ws), B, _C.stream_ptr()), "dposer_fk_joints_backward")
+        g_jr = None
+        if d_jrest is not None:                      # rest joints >= n_out move no evaluated joint
+            if not ctx.batched:
+                d_jrest = d_jrest.sum(dim=0)
+            g_jr = torch.nn.functional.pad(d_jrest, (0, 0, 0, core.J - n_out))
+        return (None, None, g_jr, d_transl, None, *dsegs)
+
+
 class _SMPLCore(nn.Module):
     """What the reference reaches as ``BodyModel.bm`` (an smplx.SMPL / SMPLH / SMPLX instance): buffers + forward.
     ``model_type`` selects the full-pose layout (``_SEGMENTS``); expression coefficients and landmarks exist for SMPL-X only."""
@@ -360,7 +408,11 @@ class _SMPLCore(nn.Module):
 
     def forward(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None, transl=None,
                 expression=None, jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True, return_full_pose=False,
-                joints_only=False, n_joints=None, **kwargs):
+                joints_only=False, n_joints=None, grad="lbs", **kwargs):
+        if grad not in ("lbs", "chain"):
+            raise ValueError(f"grad must be 'lbs' or 'chain', got {grad!r}")
+        if grad == "chain" and not joints_only:
+            raise ValueError("grad='chain' differentiates the posed joints alone: it needs joints_only=True")
         allsegs = dict(global_orient=global_orient, body_pose=body_pose, jaw_pose=jaw_pose, leye_pose=leye_pose, reye_pose=reye_pose,
                        left_hand_pose=left_hand_pose, right_hand_pose=right_hand_pose)
         segs = {name: allsegs[name] for name, _ in self.segments}      # (smplx.SMPL ignores hand / face keywords the same way)
@@ -397,6 +449,11 @@ class _SMPLCore(nn.Module):
         tr = None if transl is None else transl.contiguous().float()
         h = self._handle()
         lib = _C.lib()
+        if needs_grad and grad == "chain":
+            # the chain rule over the queried joints alone (dposer_fk_joints_backward): no vertices are formed in either direction
+            n_out = self.J if n_joints is None else int(n_joints)
+            return Struct(vertices=None, joints=_FKJointsFunction.apply(self, batched, j_rest, transl, n_out,
+                                                                        *[segs[name] for name, _ in self.segments]))
         if needs_grad:
             verts, joints = _LBSFunction.apply(self, batched, v_shaped, j_rest, transl, *[segs[name] for name, _ in self.segments])
             if joints_only:
@@ -517,6 +574,10 @@ class BodyModel(nn.Module):
         """Front half of ``forward`` for [B, 63] body poses, no vertices and no autograd: see ``_SMPLCore.lbs_front``."""
         return self.bm.lbs_front(rest=rest, betas=betas, transl=trans, global_orient=root_orient, body_pose=pose_body)
 
-    def fk_joints(self, pose_body, root_orient=None, trans=None, n_joints=22):
-        """Joints-only fast path (no vertices): [B, 63] -> [B, n_joints, 3]."""
-        return self.bm(global_orient=root_orient, body_pose=pose_body, transl=trans, joints_only=True, n_joints=n_joints).joints
+    def fk_joints(self, pose_body, root_orient=None, trans=None, n_joints=22, betas=None, grad="lbs"):
+        """Joints-only fast path (no vertices): [B, 63] -> [B, n_joints, 3].  Under autograd ``grad="lbs"`` (the default) differentiates
+        through the whole LBS forward / backward as before; ``grad="chain"`` through the kinematic chain alone
+        (``dposer_fk_joints_backward``): the same gradients for pose, root orientation, translation and betas to fp32 rounding, without
+        forming a vertex."""
+        return self.bm(betas=betas, global_orient=root_orient, body_pose=pose_body, transl=trans, joints_only=True, n_joints=n_joints,
+                       grad=grad).joints

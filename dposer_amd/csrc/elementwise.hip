@@ -948,6 +948,101 @@ template <typename T> __global__ void __launch_bounds__(256) k_guided_update(Wit
 }
 hipError_t launch_guided_update(const GuidedArgs& a, hipStream_t st) { return launch_quads(k_guided_update<float>, k_guided_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st); }
 
+// ---- DPS on observed 3D joints (dposer_joint_guided_sampler): the guided step above with the joint-residual stage of jointguide.hip as the
+// measurement.  norm = sqrt(s) with s = sum_live c |J(denormalise(y0)) - o|^2 (per row, or summed over the batch), d norm / d y0 = v / norm with
+// v = 1/2 d s / d y0 -- so v stands where k_guided_resid / k_guided_update form -mask r, and three passes stand around the stage and the dgrad:
+//   y0      the Tweedie estimate as fp32 rows for the stage
+//   dres    the upstream gradient of the backward from the stage's v, WITHOUT the 1 / norm (the backward is linear in it)
+//   update  k_guided_update reading the stored v and s where that kernel recomputes its residual
+__global__ void __launch_bounds__(256) k_joint_guided_y0(WithSde<JointGuidedArgs> d) {
+    const JointGuidedArgs& a = d.a;
+    const GuidedScal k = guided_scalars(a, d.sde);
+    const int64_t total = a.B * a.D;
+    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = o / a.D;
+        const int c = (int)(o % a.D);
+        const float score = score_of_res(d.sde, a.res[s * a.Cp + c], k.usig, k.sds);
+        a.y0[o] = tweedie_x0(a.x[o], k.sd2, score, k.mc);                              // sampling.py:200
+    }
+}
+hipError_t launch_joint_guided_y0(const JointGuidedArgs& a, hipStream_t st) {
+    const WithSde<JointGuidedArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
+    hipLaunchKernelGGL(k_joint_guided_y0, dim3(grid_for(a.B * a.D)), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+template <typename T> __global__ void __launch_bounds__(256) k_joint_guided_dres(WithSde<JointGuidedArgs> d) {
+    const JointGuidedArgs& a = d.a;
+    const int qc = a.Cp >> 2;
+    const int64_t total = a.Bpad * qc;
+    const GuidedScal k = guided_scalars(a, d.sde);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qc;
+        const int c = (int)(i % qc) * 4;
+        f32x4 dr = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                // k_guided_resid's chain with v for -mask r: / alpha, * sigma^2 (the score's share), d score / d model, / used_sigmas
+                const float gscore = (a.v[s * a.D + c + r] / k.mc) * k.sd2;
+                const float gmodel = d.sde.kind == SDE_VE ? gscore : -(gscore / k.sds);
+                dr[r] = gmodel / k.usig;
+            }
+        }
+        store_quad_ft<T>(a.dres, s, c, a.Cp, dr);
+    }
+}
+hipError_t launch_joint_guided_dres(const JointGuidedArgs& a, hipStream_t st) {
+    const WithSde<JointGuidedArgs> d = {a, make_sde_dev_at(a.sde, a.t)};
+    hipLaunchKernelGGL(a.f32 ? k_joint_guided_dres<float> : k_joint_guided_dres<__bf16>, dim3(grid_for(a.Bpad * (a.Cp >> 2), 256, 1024)), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+template <typename T> __global__ void __launch_bounds__(256) k_joint_guided_update(WithSde<JointGuidedArgs> d) {
+    const JointGuidedArgs& a = d.a;
+    const int qx = a.Dpad >> 2;
+    const int QD = (a.D + 3) >> 2;
+    const int64_t total = a.Bpad * qx;
+    const GuidedScal k = guided_scalars(a, d.sde);
+    const float norm_batch = a.norm_scope == 0 ? sqrtf(a.norm_sq[0]) : 0.f;            // torch.norm over the whole tensor (sampling.py:201)
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = i / qx;
+        const int q = (int)(i % qx);
+        const int c = q * 4;
+        f32x4 xn = {0.f, 0.f, 0.f, 0.f};
+        if (s < a.B && c < a.D) {
+            float zp[4];
+            if (!a.z_pred) normals4((uint64_t)s * QD + q, STREAM_EM_NOISE, a.step, a.seed, zp);
+            const float norm = a.norm_scope == 0 ? norm_batch : sqrtf(a.s[s]);          // "sample": every row is its own problem
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (c + r >= a.D) continue;
+                const int64_t o = s * a.D + c + r;
+                const float x0 = a.x[o];
+                const float score = score_of_res(d.sde, a.res[s * a.Cp + c + r], k.usig, k.sds);
+                float drift = (-0.5f * k.beta) * x0;                                   // sde_lib.py:98-104
+                drift = drift - (k.g * k.g) * score;
+                const float y_mean = x0 + drift * d.sde.dt;                            // sampling.py:196
+                const float y_hat = y_mean + (k.g * d.sde.sqrt_mdt) * (a.z_pred ? a.z_pred[o] : zp[r]);   // :197
+                // d norm / d x times norm: y0's direct share and the network's; norm == 0 (no live entry, or an exact fit): no guidance
+                const float gn = a.v[o] / k.mc + a.dx[o];
+                const float grad = norm == 0.0f ? 0.0f : gn / norm;
+                if (!isfinite(grad)) bad = true;                                       // :203-204
+                const float x = y_hat - a.grad_step * grad;                            // :205
+                a.x_mean[o] = y_mean;
+                if (a.traj) a.traj[o] = x;
+                a.x[o] = x;
+                xn[r] = x;
+            }
+        }
+        store_quad_ft<T>(a.xin, s, c, a.Dpad, xn);
+    }
+    if (bad) atomicMin(a.nonfinite, (int32_t)a.step);
+}
+hipError_t launch_joint_guided_update(const JointGuidedArgs& a, hipStream_t st) {
+    return launch_quads(k_joint_guided_update<float>, k_joint_guided_update<__bf16>, a, make_sde_dev_at(a.sde, a.t), st);
+}
+
 template <typename T> __global__ void __launch_bounds__(256) k_pack_rows(const float* x, void* xin, int64_t B, int64_t Bpad, int D, int Dpad) {
     const int qx = Dpad >> 2;
     const int64_t total = Bpad * qx;

@@ -2906,6 +2906,173 @@ template <typename Kin> __global__ void __launch_bounds__(64) k_fk_bwd_small(FkB
     rodrigues_bwd(rx, ry, rz, dR, dq + (b * seg_nj + li) * 3);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Joints-only FK backward: the gradient of dposer_fk_joints without a vertex in sight
+// ------------------------------------------------------------------------------------------------
+// The loss reaches the chain through the posed joints alone, so the gradient with respect to a global transform G_I = [R^G | t] has
+// two parts: the position gradient dp_I on t, and what the children hand up.  There is no skinning transform A_I = [R | t - R J_I] to
+// differentiate, so k_fk_bwd's dA terms (and the [B][J][12] gradient array they are read from) do not exist here.  The forward pass is
+// dposer_fk_joints itself, with its transforms kept in the caller's workspace ([B][n_out][12]: the parent's global rotation is the
+// 3x3 part); the joint's own rotation is re-evaluated from the pose as k_fk_bwd does.
+struct FkJointsBwdArgs {
+    const float* seg[FK_MAX_SEG];
+    float* dseg[FK_MAX_SEG];       // gradient w.r.t. each pose segment (null: not needed)
+    int seg_first[FK_MAX_SEG], seg_joints[FK_MAX_SEG], nseg;
+    const float* j_rest;           // [J][3] or [B][J][3]
+    int j_rest_batched;
+    const float* A;                // [B][n_out][12] forward transforms (dposer_fk_joints' rel_transforms)
+    const float* djoints;          // [B][ld_dj], first 3 * n_out of a row
+    int64_t ld_dj;
+    float* djrest;                 // [B][n_out][3] out or null
+    int n_out;
+    int64_t B;
+};
+// One lane per pose, joints from the last to the root with the joint index a compile-time constant (fk_bwd_step's scheme: the running
+// gradients stay in registers, and a parent adds its children in DESCENDING joint order -- one fixed order, the same bits every run).
+template <typename Kin, int I>
+__device__ __forceinline__ void fk_joints_bwd_step(const FkJointsBwdArgs& a, int64_t b, const float* jr, float (&acc)[Kin::J][12],
+                                                   float (&djr)[Kin::J][3]) {
+    constexpr int P = Kin::P[I] < 0 ? 0 : Kin::P[I];
+    int li = I;
+    const float* pose = a.seg[0];
+    float* dq = a.dseg[0];
+    int seg_nj = a.seg_joints[0];
+#pragma unroll
+    for (int k = 1; k < FK_MAX_SEG; ++k)
+        if (k < a.nseg && I >= a.seg_first[k]) { li = I - a.seg_first[k]; pose = a.seg[k]; dq = a.dseg[k]; seg_nj = a.seg_joints[k]; }
+    if (I >= a.n_out) {                                                 // not evaluated: no gradient
+        if (dq) { float* o = dq + (b * seg_nj + li) * 3; o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; }
+        return;
+    }
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    if (pose) { const float* q = pose + (b * seg_nj + li) * 3; rx = q[0]; ry = q[1]; rz = q[2]; }
+    float dRG[9], dt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dRG[3 * r + c] = acc[I][4 * r + c];
+        dt[r] = acc[I][4 * r + 3] + a.djoints[b * a.ld_dj + 3 * I + r];
+    }
+    float dR[9];                                   // gradient w.r.t. the LOCAL rotation R_I
+    if constexpr (I == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dR[k] = dRG[k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) djr[0][c] += dt[c];                                 // t_0 = J_0
+    } else {
+        const Mat3 R = rodrigues(rx, ry, rz);
+        const float* Ap = a.A + (b * a.n_out + P) * 12;                                 // P < I < n_out
+        float RP[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) RP[3 * r + c] = Ap[4 * r + c];
+        const float rel[3] = {jr[3 * I] - jr[3 * P], jr[3 * I + 1] - jr[3 * P + 1], jr[3 * I + 2] - jr[3 * P + 2]};
+        // dR_I = RP^T dRG ;  d rel = RP^T dt ;  dRG_p += dRG R_I^T + dt (x) rel ;  dt_p += dt
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dR[3 * r + c] = RP[r] * dRG[c] + RP[3 + r] * dRG[3 + c] + RP[6 + r] * dRG[6 + c];
+            const float drel = RP[r] * dt[0] + RP[3 + r] * dt[1] + RP[6 + r] * dt[2];
+            djr[I][r] += drel;
+            djr[P][r] -= drel;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                acc[P][4 * r + c] += dRG[3 * r] * R.m[3 * c] + dRG[3 * r + 1] * R.m[3 * c + 1] + dRG[3 * r + 2] * R.m[3 * c + 2] + dt[r] * rel[c];
+            acc[P][4 * r + 3] += dt[r];
+        }
+    }
+    if (a.djrest) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.djrest[(b * a.n_out + I) * 3 + c] = djr[I][c];    // every child (index > I) has been processed
+    }
+    if (!dq) return;
+    rodrigues_bwd(rx, ry, rz, dR, dq + (b * seg_nj + li) * 3);
+}
+template <typename Kin, int I>
+__device__ __forceinline__ void fk_joints_bwd_chain(const FkJointsBwdArgs& a, int64_t b, const float* jr, float (&acc)[Kin::J][12],
+                                                    float (&djr)[Kin::J][3]) {
+    fk_joints_bwd_step<Kin, I>(a, b, jr, acc, djr);
+    __builtin_amdgcn_sched_barrier(0);             // (as in fk_bwd_chain: one joint's loads at a time)
+    asm volatile("" ::: "memory");
+    if constexpr (I > 0) fk_joints_bwd_chain<Kin, I - 1>(a, b, jr, acc, djr);
+}
+template <typename Kin> __global__ void __launch_bounds__(64, 1) k_fk_joints_bwd(FkJointsBwdArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    constexpr int J = Kin::J;
+    const float* jr = a.j_rest_batched ? a.j_rest + b * J * 3 : a.j_rest;
+    float acc[J][12], djr[J][3];
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) acc[i][k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) djr[i][k] = 0.f;
+    }
+    fk_joints_bwd_chain<Kin, J - 1>(a, b, jr, acc, djr);
+}
+
+// workspace: the forward's transforms [B][n_out][12] and its posed joints [B][n_out][3] (fp32) -- 60 bytes per joint and pose
+extern "C" int64_t dposer_fk_joints_backward_workspace_bytes(dposer_body_t h, int32_t n_out, int64_t batch) {
+    if (!h || n_out < 1 || n_out > h->d.num_joints || batch < 1) return 0;
+    return batch * n_out * 15 * (int64_t)sizeof(float);
+}
+// The reverse walk alone, on transforms a dposer_fk_joints call with rel_transforms has left in A (kernels_api.h: dposer_joint_guide_stage
+// runs its residual between the two).  The caller has checked the arguments.
+int fk_joints_backward_launch(dposer_body_t h, const float* const* pose_segments_host, const int32_t* segment_joints_host, int32_t num_segments,
+                              const float* j_rest, int32_t j_rest_batched, const float* A, const float* d_joints, int64_t d_joints_ld, int32_t n_out,
+                              float* const* d_pose_segments_host, float* d_jrest, int64_t batch, hipStream_t st) {
+    FkJointsBwdArgs g;
+    std::memset(&g, 0, sizeof(g));
+    int first = 0;
+    for (int i = 0; i < num_segments; ++i) {
+        g.seg[i] = pose_segments_host[i];
+        g.dseg[i] = d_pose_segments_host[i];
+        g.seg_first[i] = first;
+        g.seg_joints[i] = segment_joints_host[i];
+        first += segment_joints_host[i];
+    }
+    g.nseg = num_segments; g.j_rest = j_rest; g.j_rest_batched = j_rest_batched; g.A = A; g.djoints = d_joints; g.ld_dj = d_joints_ld;
+    g.djrest = d_jrest; g.n_out = n_out; g.B = batch;
+    const dim3 grid((unsigned)ceil_div(batch, 64));
+    if (h->kind == 0) hipLaunchKernelGGL(k_fk_joints_bwd<KinSMPL>, grid, dim3(64), 0, st, g);
+    else if (h->kind == 1) hipLaunchKernelGGL(k_fk_joints_bwd<KinSMPLH>, grid, dim3(64), 0, st, g);
+    else hipLaunchKernelGGL(k_fk_joints_bwd<KinSMPLX>, grid, dim3(64), 0, st, g);
+    DP_CHECK_HIP(hipGetLastError());
+    return DPOSER_OK;
+}
+int body_num_joints(dposer_body_t h) { return h ? h->d.num_joints : 0; }
+
+extern "C" int dposer_fk_joints_backward(dposer_body_t h, const float* const* pose_segments_host, const int32_t* segment_joints_host,
+                                         int32_t num_segments, const float* j_rest, int32_t j_rest_batched, const float* d_joints,
+                                         int64_t d_joints_ld, int32_t n_out, float* const* d_pose_segments_host, float* d_jrest,
+                                         void* workspace, int64_t batch, void* stream) {
+    DP_RANGE();
+    DP_CHECK_ARG(h, "null handle");
+    DP_CHECK_ARG(pose_segments_host && segment_joints_host && j_rest && d_joints && d_pose_segments_host, "null argument");
+    DP_CHECK_ARG(num_segments >= 1 && num_segments <= FK_MAX_SEG, "1..8 pose segments");
+    DP_CHECK_ARG(batch > 0, "batch must be positive");
+    DP_CHECK_ARG(n_out >= 1 && n_out <= h->d.num_joints, "n_out must be in 1..num_joints");
+    DP_CHECK_ARG(d_joints_ld >= (int64_t)n_out * 3, "d_joints_ld must be at least 3 * n_out");
+    DP_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0, "workspace must be non-null and 16-byte aligned");
+    int first = 0;
+    for (int i = 0; i < num_segments; ++i) {
+        DP_CHECK_ARG(segment_joints_host[i] >= 1, "a pose segment has at least one joint");
+        first += segment_joints_host[i];
+    }
+    DP_CHECK_ARG(first == h->d.num_joints, "pose segments must cover all joints of the kinematic tree");
+    float* A = static_cast<float*>(workspace);
+    float* posed = A + batch * n_out * 12;
+    // forward, transforms kept: the same kernels, in the same order, as a dposer_fk_joints call with rel_transforms
+    DP_TRY(dposer_fk_joints(h, pose_segments_host, segment_joints_host, num_segments, j_rest, j_rest_batched, nullptr, posed, A, n_out, batch, stream));
+    return fk_joints_backward_launch(h, pose_segments_host, segment_joints_host, num_segments, j_rest, j_rest_batched, A, d_joints, d_joints_ld, n_out,
+                                     d_pose_segments_host, d_jrest, batch, (hipStream_t)stream);
+}
+
 // d pose_feature: sum of the split-K slabs of the d_off @ posedirs^T GEMM, [nsplit][Bpad][ld] -> slab 0 (fixed order)
 __global__ void __launch_bounds__(256) k_sum_slabs(float* slabs, int64_t slab_elems, int nsplit) {
     const int64_t n4 = slab_elems >> 2;

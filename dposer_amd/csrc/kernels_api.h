@@ -270,6 +270,25 @@ struct GuidedArgs : UpdateCommon {
 hipError_t launch_guided_resid(const GuidedArgs& a, int* nblocks, hipStream_t st);
 hipError_t launch_guided_update(const GuidedArgs& a, hipStream_t st);
 
+// ---- one-call DPS sampler on observed 3D joints: the passes around the joint-residual stage (jointguide.hip) and the dgrad ----
+struct JointGuidedArgs : UpdateCommon {
+    // res: post_dense output at x, kept with the activations; x_mean: out = y_mean
+    float* y0;             // y0 pass: [B][D] Tweedie estimate, the stage's input
+    const float* v;        // dres / update pass: [B][D] the stage's 1/2 d s / d y0
+    const float* s;        // update pass: [B] the stage's sums (norm_scope 1: norm_b = sqrt(s[b]))
+    const float* norm_sq;  // update pass, norm_scope 0: [1] = sum_b s[b]
+    void* dres;            // dres pass: FT [Bpad][Cp], d norm / d res TIMES norm
+    const float* dx;       // update pass: [B][D] = J_res^T dres
+    float* traj;           // [B][D] slot of this step or null
+    const float* z_pred;   // injected predictor noise [B][D] or null (-> Philox STREAM_EM_NOISE at `step`)
+    int32_t* nonfinite;    // update pass: atomicMin of `step` where an element of the gradient is not finite
+    float grad_step;
+    int norm_scope;        // 0: one norm over the batch, 1: one per row
+};
+hipError_t launch_joint_guided_y0(const JointGuidedArgs& a, hipStream_t st);
+hipError_t launch_joint_guided_dres(const JointGuidedArgs& a, hipStream_t st);
+hipError_t launch_joint_guided_update(const JointGuidedArgs& a, hipStream_t st);
+
 struct DsmArgs {           // get_sde_loss_fn tail (losses.py:121-131) + d loss / d res
     const float* res;      // [Bpad][Cp]
     const float* t;        // [Bpad]
@@ -399,3 +418,11 @@ struct AdamPackArgs {
     int write_through;    // 1: parameters / moments / EMA leave as write-through stores (no dirty L2 lines behind the launch)
 };
 hipError_t launch_adam_pack(const AdamPackArgs& a, hipStream_t st);
+
+// ---- body-model internals that jointguide.hip shares with fk.hip (implemented there) ----------------------------------------------------
+int body_num_joints(dposer_body_t h);                                 // 0 for a null handle
+// the reverse walk of dposer_fk_joints_backward alone, on the transforms A [B][n_out][12] of a dposer_fk_joints(rel_transforms = A) call over
+// the same segments; arguments as in that entry, already checked
+int fk_joints_backward_launch(dposer_body_t h, const float* const* pose_segments_host, const int32_t* segment_joints_host, int32_t num_segments,
+                              const float* j_rest, int32_t j_rest_batched, const float* A, const float* d_joints, int64_t d_joints_ld, int32_t n_out,
+                              float* const* d_pose_segments_host, float* d_jrest, int64_t batch, hipStream_t st);

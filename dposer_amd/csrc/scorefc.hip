@@ -2165,6 +2165,71 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
     return DPOSER_OK;
 }
 
+// DPS on observed 3D joints (include/dposer_hip.h has the contract): dposer_guided_sampler's loop with the joint-residual stage as the
+// measurement.  Per loop index: network with kept activations -> y0 rows -> dposer_joint_guide_stage (s, v) -> [batch scope: fixed-order sum of
+// s] -> upstream gradient from v -> dgrad-only backward -> update, which leaves the new state FT-tiled in w.xin.
+//   scratch: the stage's | y0 [B][63] | v [B][63] | s [B]
+extern "C" int64_t dposer_joint_guided_scratch_bytes(int64_t batch) {
+    return batch < 1 ? 0 : dposer_joint_guide_stage_scratch_bytes(batch) + batch * (2 * 63 + 1) * (int64_t)sizeof(float);
+}
+extern "C" int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
+                                           float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, dposer_body_t body,
+                                           int32_t norm_mode, const float* norm_a, const float* norm_b, const float* root_orient, const float* transl,
+                                           const float* j_rest, int32_t j_rest_batched, const float* joints_obs, const float* joints_conf,
+                                           const int32_t* obs_rows, int32_t n_obs, int32_t norm_scope, const float* noise, uint64_t seed, float* traj,
+                                           int32_t traj_stride, float grad_step, int32_t* nonfinite_step, void* scratch, const float* freq,
+                                           const float* sigmas, int64_t B, void* stream) {
+    SharedT c;
+    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
+    DP_CHECK_ARG(body && j_rest && joints_obs, "body, j_rest and joints_obs are required");
+    DP_CHECK_ARG(nonfinite_step, "nonfinite_step is required");
+    if (sde->kind == DPOSER_SDE_VE || sde->kind == DPOSER_SDE_VE_DISCRETE || sde->kind == DPOSER_SDE_VP_DISCRETE)
+        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, std::string(__func__) + ": the joint-guided sampler takes the continuous sub-VP and VP score functions");
+    DP_CHECK_ARG(sde->kind == DPOSER_SDE_SUBVP || sde->kind == DPOSER_SDE_VP, "unknown SDE kind");
+    if (h->D != 63)
+        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, std::string(__func__) + ": the network must work on 21 axis-angle joints (63 inputs); rot6d (126) is not supported");
+    DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
+    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
+    DP_CHECK_ARG(norm_scope == 0 || norm_scope == 1, "norm_scope must be 0 (batch) or 1 (sample)");
+    DP_CHECK_ARG(n_obs >= 1 && n_obs <= 22, "n_obs must be in 1..22");
+    DP_CHECK_ARG(norm_mode == 0 || ((norm_mode == 1 || norm_mode == 2) && norm_a && norm_b), "bad normaliser");
+    DP_CHECK_ARG(scratch && ((uintptr_t)scratch & 15) == 0, "scratch must be non-null and 16-byte aligned");
+    DP_CHECK_ARG(body_num_joints(body) > 22, "the body's tree must hold the 22 body joints first");
+    DP_CHECK_ARG(B < ((int64_t)1 << 31), "batch must be below 2^31");
+    const int n_run = steps_to_run(sde->N, start_step, n_steps);
+    c.open(sde, DPOSER_WS_GUIDED, n_run);
+    if (n_run == 0) return DPOSER_OK;
+    Ws& w = c.w;
+    hipStream_t st = c.st;
+    const char* packed = c.packed;
+    DP_TRY(c.table(timesteps_host + start_step, n_run, freq));
+    const int64_t BD = B * h->D;
+    float* y0 = reinterpret_cast<float*>(static_cast<char*>(scratch) + dposer_joint_guide_stage_scratch_bytes(B));
+    float* v = y0 + BD;
+    float* s = v + BD;
+    JointGuidedArgs ga{};
+    static_cast<UpdateCommon&>(ga) = update_common(c, sigmas, x, x_mean, seed);
+    ga.y0 = y0; ga.v = v; ga.s = s; ga.norm_sq = w.scalar; ga.dres = w.dres; ga.dx = w.zbuf;
+    ga.nonfinite = nonfinite_step; ga.grad_step = grad_step; ga.norm_scope = norm_scope;
+    DP_CHECK_HIP(launch_pack_rows(x, w.xin, B, w.Bpad, h->D, h->Dpad, h->f32, st));
+    for (int i = 0; i < n_run; ++i) {
+        const int gi = start_step + i;
+        ga.t = timesteps_host[gi]; ga.step = (uint32_t)gi;
+        ga.z_pred = noise ? noise + (int64_t)i * BD : nullptr;
+        ga.traj = traj_slot(traj, i, traj_stride, BD);
+        DP_TRY(forward_core_guided(h, flat, packed, w, i, B, st));
+        DP_CHECK_HIP(launch_joint_guided_y0(ga, st));
+        DP_TRY(dposer_joint_guide_stage(body, y0, 63, norm_mode, norm_a, norm_b, root_orient, transl, j_rest, j_rest_batched, joints_obs, joints_conf,
+                                        obs_rows, n_obs, s, v, scratch, B, stream));
+        if (norm_scope == 0) DP_CHECK_HIP(launch_sum_partials(s, (int)B, w.scalar, st));
+        DP_CHECK_HIP(launch_joint_guided_dres(ga, st));
+        DP_TRY(backward_core(h, flat, packed, w, B, false, 0, 0, nullptr, w.zbuf, nullptr, st));
+        DP_CHECK_HIP(launch_joint_guided_update(ga, st));
+    }
+    return DPOSER_OK;
+}
+
 extern "C" int dposer_grad_sqnorm(const float* grad, int64_t n, float* scratch, void* stream) {
     DP_RANGE();
     DP_CHECK_ARG(grad && scratch && n >= 0, "bad argument");

@@ -185,3 +185,84 @@ def evaluate_completion(model, sde, normalizer, body_model, poses, *, part="legs
         done += batch_size
     # fixed name list: a rank whose shard is shorter than one batch (drop_last) has no results to learn the names from
     return ddp.reduce_metric_means(results, device=dev, names=("mpjpe_body", "mpvpe_all")), done
+
+
+def joint_residual_stage(body_model, normalizer, y0, joints3d, *, joints_conf=None, obs_joints=None, root_orient=None, trans=None, betas=None):
+    """The measurement stage of guidance by observed 3D joints, for a batch of normalised poses: ``dposer_joint_guide_stage``, one library
+    call.  ``y0`` [B, 63] normalised body poses (axis-angle networks only); ``joints3d`` [B, n_obs, 3]; ``joints_conf`` [B, n_obs] or
+    [n_obs]-broadcastable (an entry counts iff its confidence is > 0; what lies under a dead entry may be NaN); ``obs_joints``: the n_obs
+    distinct body joints in [0, 22) the columns observe (default 0 .. n_obs - 1); ``root_orient`` / ``trans`` [B, 3]; ``betas`` [B, n].
+    Returns ``(s [B], v [B, 63])``: s = sum_live c |J(denormalise(y0)) - o|^2 and v = 1/2 ds/dy0 -- the chain rule over the joints alone
+    (``dposer_fk_joints_backward``), no vertices.  Shapes and ``obs_joints`` are checked before any device work."""
+    from ._fused import normalizer_tables
+    from .motion_denoising import _partial_observation
+    if y0.dim() != 2 or y0.shape[1] != 63:
+        raise ValueError(f"y0 must be [B, 63] (21 axis-angle body joints; rot6d networks are not supported), got {list(y0.shape)}")
+    B = int(y0.shape[0])
+    if joints3d.dim() != 3 or joints3d.shape[0] != B or joints3d.shape[2] != 3 or not 1 <= joints3d.shape[1] <= 22:
+        raise ValueError(f"joints3d must be [{B}, 1..22, 3], got {list(joints3d.shape)}")
+    for name, t in (("root_orient", root_orient), ("trans", trans)):
+        if t is not None and tuple(t.shape) != (B, 3):
+            raise ValueError(f"{name} must be [{B}, 3], got {list(t.shape)}")
+    conf, rows = _partial_observation(joints3d, joints_conf, obs_joints, 22)
+    _C.require_gpu(y0, "y0")
+    dev = y0.device
+    core = body_model.bm
+    with torch.no_grad():
+        _, j_rest, batched = core.rest_shape(betas, None)
+    f32 = lambda t: None if t is None else t.detach().to(dev).contiguous().float()
+    y, obs, root, tr, jr = f32(y0), f32(joints3d), f32(root_orient), f32(trans), f32(j_rest)
+    mode, na, nb = normalizer_tables(normalizer, y)
+    rows_d = None if rows is None else torch.tensor(rows, dtype=torch.int32, device=dev)
+    lib = _C.lib()
+    s = torch.empty(B, dtype=torch.float32, device=dev)
+    v = torch.empty(B, 63, dtype=torch.float32, device=dev)
+    scratch = torch.empty(lib.dposer_joint_guide_stage_scratch_bytes(B), dtype=torch.uint8, device=dev)
+    _C.check(lib.dposer_joint_guide_stage(core._handle(), _C.ptr(y), 63, mode, _C.ptr(na), _C.ptr(nb), _C.ptr(root), _C.ptr(tr), _C.ptr(jr),
+                                          1 if batched else 0, _C.ptr(obs), _C.ptr(conf), _C.ptr(rows_d), int(obs.shape[1]), _C.ptr(s), _C.ptr(v),
+                                          _C.ptr(scratch), B, _C.stream_ptr()), "dposer_joint_guide_stage")
+    return s, v
+
+
+def sample_from_joints(model, sde, normalizer, body_model, joints3d, *, joints_conf=None, obs_joints=None, hypo=1, grad_step=1.0, norm="sample",
+                       gt_poses=None, root_orient=None, trans=None, betas=None, continuous=True, eps=1e-3, noise=None, seed=None, z=None, start_step=0):
+    """``hypo`` plausible bodies for every set of observed 3D joints: DPS under the DPoser prior with the posed joints as the measurement
+    (``sampling.get_joint_guided_sampler``), all hypotheses in one batch -- what ``evaluate_completion(hypo=K)`` does for masked poses.
+
+    ``joints3d`` [B, n_obs, 3] (NaN allowed under a confidence that is not > 0: ``utils.misc.occlude_joints`` makes such inputs),
+    ``joints_conf`` [B, n_obs] or None, ``obs_joints`` the observed tree joints (default 0 .. n_obs - 1); ``root_orient`` / ``trans`` [B, 3],
+    ``betas`` [B, n].  The observation is tiled over the hypotheses (rows b * hypo + k); ``noise`` [N - start_step, 1, B * hypo, 63] / ``z`` [B * hypo, 63]
+    inject the draws and ``start_step`` enters the loop late (``z`` is then the state at that index).  Returns a dict: ``poses`` [B, hypo, 63] axis-angle (de-normalised), ``joint_error`` [B, hypo] the mean distance in
+    metres between the posed and the observed joints over the live entries (NaN for a sample without one) and, with ``gt_poses``
+    [B, 63], ``mpjpe`` / ``mpvpe`` [B]: the minimum over the hypotheses through ``utils.metric.pose_pair_errors``."""
+    from ..algorithms.advanced import sampling
+    from ..utils.metric import pose_pair_errors
+    from .motion_denoising import _partial_observation
+    if joints3d.dim() != 3 or joints3d.shape[2] != 3:
+        raise ValueError(f"joints3d must be [B, n_obs, 3], got {list(joints3d.shape)}")
+    if int(hypo) < 1:
+        raise ValueError(f"hypo must be >= 1, got {hypo}")
+    B, K = int(joints3d.shape[0]), int(hypo)
+    conf, rows = _partial_observation(joints3d, joints_conf, obs_joints, 22)          # (host checks before any device work)
+    if gt_poses is not None and tuple(gt_poses.shape) != (B, 63):
+        raise ValueError(f"gt_poses must be [{B}, 63], got {list(gt_poses.shape)}")
+    tile = lambda t: None if t is None else t.repeat_interleave(K, dim=0)
+    dev = joints3d.device
+    fn = sampling.get_joint_guided_sampler(sde, (B * K, 63), body_model, normalizer, grad_step=grad_step, norm=norm, continuous=continuous,
+                                           denoise=True, eps=eps, device=dev)
+    obs_t, conf_t, root_t, tr_t, betas_t = tile(joints3d), tile(conf), tile(root_orient), tile(trans), tile(betas)
+    _, x = fn(model, obs_t, conf_t, rows, root_t, tr_t, betas_t, z=z, start_step=start_step, traj_stride=0, noise=noise, seed=seed)
+    with torch.no_grad():
+        poses = normalizer.offline_denormalize(x)
+        joints = body_model.fk_joints(poses, root_orient=root_t, trans=tr_t, betas=betas_t)
+        idx = torch.arange(obs_t.shape[1], device=dev) if rows is None else torch.tensor(rows, dtype=torch.long, device=dev)
+        live = torch.ones(obs_t.shape[:2], dtype=torch.bool, device=dev) if conf_t is None else conf_t > 0
+        d = joints[:, idx] - torch.where(live[..., None], obs_t.float(), torch.zeros_like(obs_t, dtype=torch.float32))
+        dist = torch.where(live, torch.sqrt((d * d).sum(dim=2)), torch.zeros_like(d[..., 0]))
+        cnt = live.sum(dim=1)
+        err = torch.where(cnt > 0, dist.sum(dim=1) / cnt.clamp_min(1), torch.full_like(dist[:, 0], float("nan")))
+        out = {"poses": poses.reshape(B, K, 63), "joint_error": err.reshape(B, K)}
+        if gt_poses is not None:
+            pe = pose_pair_errors(body_model, gt_poses.to(dev).float(), out["poses"], betas=betas)
+            out["mpjpe"], out["mpvpe"] = pe["mpjpe"], pe["mpvpe"]
+    return out

@@ -551,6 +551,80 @@ int dposer_fk_joints(dposer_body_t h, const float* const* pose_segments_host, co
                      int32_t num_segments, const float* j_rest, int32_t j_rest_batched, const float* transl,
                      float* joints, float* rel_transforms, int32_t n_out, int64_t batch, void* stream);
 
+/* Gradient of dposer_fk_joints with respect to the pose segments and the rest joints, given the gradient with respect to the
+ * posed joints -- the chain rule over the n_out joints alone: no vertex, no skinning, no blend GEMM (the LBS backward needs more
+ * than 125 KB per pose for the vertices; this call reads and writes 60 bytes per joint and pose of workspace besides its arguments).
+ *   pose_segments_host / segment_joints_host / j_rest / j_rest_batched: as in dposer_fk_joints (the same values as in the forward call);
+ *   d_joints [B][d_joints_ld] floats, d_joints_ld >= 3 * n_out: the first 3 * n_out of a row are the gradient with respect to the
+ *     posed joints [0, n_out);
+ *   d_pose_segments_host[i]: DEVICE pointer to [B, segment_joints[i]*3] or NULL (not wanted); the axis-angle gradient of segment i
+ *     is written there, with zeros for joints >= n_out;
+ *   d_jrest [B, n_out, 3] out or NULL: the gradient with respect to the rest joints [0, n_out) of every pose (a caller with shared
+ *     rest joints sums over the batch);
+ *   workspace: >= dposer_fk_joints_backward_workspace_bytes(h, n_out, batch) bytes, 16-byte aligned, caller-owned; contents are
+ *     scratch (the forward's transforms [B][n_out][12] and posed joints).
+ * The translation's gradient is the sum of d_joints over the joints and stays with the caller.  Rotations are those of
+ * dposer_fk_joints (rodrigues with smplx's + 1e-8) and rodrigues_bwd.  One lane walks one pose's chain from the last joint to the
+ * root and a parent adds its children in descending joint order: one fixed summation order, the same bits for the same inputs.
+ * Every argument is checked before the first launch; no allocation, no synchronisation. */
+int64_t dposer_fk_joints_backward_workspace_bytes(dposer_body_t h, int32_t n_out, int64_t batch);
+int dposer_fk_joints_backward(dposer_body_t h, const float* const* pose_segments_host, const int32_t* segment_joints_host,
+                              int32_t num_segments, const float* j_rest, int32_t j_rest_batched, const float* d_joints,
+                              int64_t d_joints_ld, int32_t n_out, float* const* d_pose_segments_host, float* d_jrest,
+                              void* workspace, int64_t batch, void* stream);
+
+/* The joint-residual stage of a 3D-joint measurement on a normalised body pose: what a sampler or a fitting loop guided by observed 3D
+ * joints evaluates once per step.  Per pose b:
+ *   pose = denormalise(y0[b]),  y0 [B, 63]: 21 body joints, axis-angle, in the network's normalised space;
+ *     norm_mode / norm_a / norm_b exactly as in dposer_motion_denoise_args: 0 none / 1 z-score (mean, std) / 2 min-max (min, max), [63];
+ *   J = the 22 posed joints of dposer_fk_joints over (root_orient [B,3] or NULL = identity, pose, every other joint at rest), rest joints
+ *     j_rest [J,3] or [B,J,3] (j_rest_batched), + transl [B,3] if not NULL;  `body` is any supported tree (its first 22 joints are the body).
+ * The observation rule is the motion-denoising one (PARTIAL OBSERVATIONS below), restated:
+ *   joints_obs [B, n_obs, 3];  joints_conf [B, n_obs] or NULL = 1;  obs_rows DEVICE [n_obs]: distinct tree joints in [0, 22), or NULL =
+ *   0 .. n_obs-1 (the caller checks range and distinctness; a row outside [0, 22) counts as not live and is never dereferenced);
+ *   an entry is LIVE iff c > 0 -- false for 0, for negatives and for NaN;  a dead entry's observation may be NaN or Inf and never
+ *   enters a sum.
+ * Outputs:
+ *   s[b] = sum_live c |J[rows[j]] - o_j|^2            [B]
+ *   v[b] = 1/2 d s[b] / d y0[b]                        [B, 63]: FK forward, residual, the reverse walk of dposer_fk_joints_backward, the
+ *                                                      normaliser's scale.  A pose without a live entry gets s = 0, v = 0.
+ * fp32 throughout; one lane sums a pose's entries in ascending column order and walks its chain: the same inputs give the same bits.
+ * data_dim must be 63: a rot6d network (126) returns DPOSER_ERR_UNSUPPORTED.  n_obs in 1..22.  scratch: caller-owned,
+ * >= dposer_joint_guide_stage_scratch_bytes(batch), 16-byte aligned.  Every argument is checked before the first launch; no allocation,
+ * no synchronisation. */
+int64_t dposer_joint_guide_stage_scratch_bytes(int64_t batch);
+int dposer_joint_guide_stage(dposer_body_t body, const float* y0, int32_t data_dim, int32_t norm_mode, const float* norm_a,
+                             const float* norm_b, const float* root_orient, const float* transl, const float* j_rest,
+                             int32_t j_rest_batched, const float* joints_obs, const float* joints_conf, const int32_t* obs_rows,
+                             int32_t n_obs, float* s, float* v, void* scratch, int64_t batch, void* stream);
+
+/* DPS on observed 3D joints, every step in one call: dposer_guided_sampler's loop with the stage above, dposer_joint_guide_stage, as the
+ * measurement operator instead of a pose-space mask.  Arguments: those of dposer_guided_sampler without
+ * observation / mask / project; the stage's inputs (body .. n_obs, same meaning, same observation rule); norm_scope; a caller-owned
+ * scratch of >= dposer_joint_guided_scratch_bytes(B) bytes, 16-byte aligned.  Per loop index i, t = timesteps_host[i], dt = -1/N, in the
+ * notation of dposer_guided_sampler's contract:
+ *   score = score_fn(x, t) with kept activations;  y_mean, y_hat as above;  y0 = (x + sigma^2 score) / alpha;
+ *   (s[b], v[b]) = the stage at y0:  s[b] = sum_live c |J_rows[j](denormalise(y0[b])) - o_j|^2,  v[b] = 1/2 d s[b] / d y0[b];
+ *   norm_scope 0 ("batch"):  norm = sqrt(sum_b s[b]), the reference's torch.norm over the whole tensor (sampling.py:201), the sum taken
+ *     by one block in a fixed order;   norm_scope 1 ("sample"):  norm_b = sqrt(s[b]) -- every row is its own problem and its
+ *     guidance does not depend on its batch mates;
+ *   grad = (v / alpha + J_score^T [(sigma^2 / alpha) v]) / norm   (the dgrad's upstream gradient is written without the 1 / norm, as
+ *     k_guided_resid does);  norm == 0 gives grad = 0: a row (scope 1) or a batch (scope 0) without a live entry is sampled unconditionally;
+ *   x = y_hat - grad_step grad,  x_mean = y_mean.
+ * Trajectory slots and nonfinite_step behave as in dposer_guided_sampler (a NaN observation under a positive confidence raises the
+ * flag at its loop index).  noise [n_run][1][B][D] or NULL = Philox STREAM_EM_NOISE at i.  No MCG projection: there is no pose-space
+ * mask.  Workspace DPOSER_WS_GUIDED with n_run table rows; `packed` holds the backward copies.  Continuous sub-VP and VP only: VE and the
+ * discrete kinds return DPOSER_ERR_UNSUPPORTED, and so does a network whose data_dim is not 63 (rot6d: 126).  Every argument is checked
+ * before anything is launched; no allocation, no synchronisation. */
+int64_t dposer_joint_guided_scratch_bytes(int64_t batch);
+int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed, void* ws, const dposer_sde_desc* sde, float* x,
+                                float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, dposer_body_t body,
+                                int32_t norm_mode, const float* norm_a, const float* norm_b, const float* root_orient, const float* transl,
+                                const float* j_rest, int32_t j_rest_batched, const float* joints_obs, const float* joints_conf,
+                                const int32_t* obs_rows, int32_t n_obs, int32_t norm_scope, const float* noise, uint64_t seed, float* traj,
+                                int32_t traj_stride, float grad_step, int32_t* nonfinite_step, void* scratch, const float* freq,
+                                const float* sigmas, int64_t B, void* stream);
+
 /* Linear blend skinning -- smplx/lbs.py lbs() + SMPLX.forward joint assembly, as called from
  * lib/body_model/body_model.py:75-103 (BodyModel.forward) and lib/body_model/smpl.py:67-77.
  *   posedirs_packed: dposer_lbs_pack_posedirs(posedirs [(J-1)*9, V*3]) (MFMA fragment order, fp32);
