@@ -304,6 +304,11 @@ SIGNATURES = {
                                               i32, i32, vp, u64, vp, i32, f32, vp, vp, vp, vp, i64, vp]),
     "dposer_joint_guide_stage_scratch_bytes": (i64, [i64]),
     "dposer_joint_guide_stage": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, vp]),
+    "dposer_keypoint_guided_scratch_bytes": (i64, [i64]),
+    "dposer_keypoint_guided_sampler": (C.c_int, [vp, vp, vp, vp, C.POINTER(SdeDesc), vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                                 i32, vp, vp, f32, f32, i32, vp, u64, vp, i32, f32, vp, vp, vp, vp, i64, vp]),
+    "dposer_keypoint_guide_stage_scratch_bytes": (i64, [i64]),
+    "dposer_keypoint_guide_stage": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, f32, f32, vp, vp, vp, i64, vp]),
     "dposer_lbs_posedirs_packed_bytes": (i64, [vp]),
     "dposer_lbs_pack_posedirs": (C.c_int, [vp, vp, vp, vp]),
     "dposer_lbs_workspace_bytes": (i64, [vp, i64]),

@@ -941,6 +941,195 @@ def get_joint_guided_sampler(sde, shape, body_model, normalizer, grad_step=1.0, 
     return joint_guided_sampler
 
 
+def _keypoint_guided_problem(keypoints2d, keypoints_conf, obs_joints, cam_t, camera_center, focal_length, sigma, z_near, root_orient, betas, B):
+    """Host checks of a 2D-keypoint observation for ``B`` poses and its camera (shapes, ``obs_joints`` range and distinctness, the scalars --
+    before any device work): (keypoints [B, n_obs, 2], conf [B, n_obs] or None, rows list or None, focal [B] float32 on the keypoints'
+    device).  ``focal_length``: a number, or a tensor of 1 or B values."""
+    from ...tasks.motion_denoising import _partial_observation
+    if keypoints2d.dim() != 3 or tuple(keypoints2d.shape[::2]) != (B, 2) or not 1 <= keypoints2d.shape[1] <= 22:
+        raise ValueError(f"keypoints2d must be [{B}, 1..22, 2], got {list(keypoints2d.shape)}")
+    if cam_t is None or camera_center is None:
+        raise ValueError("cam_t [B, 3] and camera_center [B, 2] are required")
+    for name, t, n in (("cam_t", cam_t, 3), ("camera_center", camera_center, 2), ("root_orient", root_orient, 3)):
+        if t is not None and tuple(t.shape) != (B, n):
+            raise ValueError(f"{name} must be [{B}, {n}], got {list(t.shape)}")
+    if betas is not None and (betas.dim() != 2 or betas.shape[0] != B):
+        raise ValueError(f"betas must be [{B}, n], got {list(betas.shape)}")
+    if not float(z_near) > 0 or not np.isfinite(float(z_near)):
+        raise ValueError(f"z_near must be positive and finite, got {z_near}")
+    if not (float(sigma) <= 0 or 1e-18 <= float(sigma) <= 1e18):
+        raise ValueError(f"sigma must be <= 0 (no robustifier) or in [1e-18, 1e18], got {sigma}")
+    focal = torch.as_tensor(focal_length, dtype=torch.float32).reshape(-1)
+    if focal.numel() not in (1, B):
+        raise ValueError(f"focal_length must be a number or [{B}], got {list(focal.shape)}")
+    focal = focal.expand(B).contiguous().to(keypoints2d.device)
+    try:
+        conf, rows = _partial_observation(keypoints2d, keypoints_conf, obs_joints, 22)
+    except ValueError as e:                          # the shared rule's messages, in this function's argument names
+        raise ValueError(str(e).replace("joints3d", "keypoints2d").replace("joints_conf", "keypoints_conf")) from None
+    return keypoints2d, conf, rows, focal
+
+
+def fused_keypoint_guided_sample(model, sde, x, timesteps, body_model, normalizer, keypoints2d, *, keypoints_conf=None, obs_rows=None, cam_t,
+                                 camera_center, focal, sigma=100.0, z_near=0.1, root_orient=None, betas=None, norm="sample", grad_step=1.0,
+                                 start_step=0, run_steps=-1, noise=None, seed=0, traj_stride=0, continuous=True):
+    """dposer_keypoint_guided_sampler: loop indices [start_step, start_step + run_steps) (run_steps < 0: to N) of DPS on observed 2D
+    keypoints in ONE library call, then one 4-byte read of the non-finite flag.  x [B, 63] initial state (consumed); ``keypoints2d``
+    [B, n_obs, 2] pixels, ``keypoints_conf`` [B, n_obs] or None, ``obs_rows`` a list of n_obs distinct joints in [0, 22) or None, ``cam_t``
+    [B, 3], ``camera_center`` [B, 2], ``focal`` [B] -- already checked (``get_keypoint_guided_sampler`` does).  Returns (trajs or None, x, x_mean)."""
+    from ...tasks._fused import normalizer_tables
+    N = int(sde.N)
+    n_run = N - start_step if (run_steps < 0 or run_steps > N - start_step) else int(run_steps)
+    _C.require_gpu(keypoints2d, "keypoint-guided sampler observation")
+    p = _fused_prelude(model, sde, x, timesteps, n_run, traj_stride, continuous, None, None, noise, with_backward=True)
+    if p.B == 0:
+        return p.traj, p.x, p.x_mean
+    eng, B, dev = p.eng, p.B, x.device
+    core = body_model.bm
+    with torch.no_grad():
+        _, j_rest, batched = core.rest_shape(betas, None)
+    f32 = lambda t: None if t is None else t.detach().to(dev).contiguous().float()
+    kp, conf, root, tr, jr, fo, ce = f32(keypoints2d), f32(keypoints_conf), f32(root_orient), f32(cam_t), f32(j_rest), f32(focal), f32(camera_center)
+    mode, na, nb = normalizer_tables(normalizer, p.x)
+    rows_d = None if obs_rows is None else torch.tensor([int(r) for r in obs_rows], dtype=torch.int32, device=dev)
+    ws = eng.workspace(B, _C.WS_GUIDED, max(n_run, 1), dev)
+    scratch = torch.empty(eng.lib.dposer_keypoint_guided_scratch_bytes(B), dtype=torch.uint8, device=dev)
+    flag = torch.full((1,), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+    _C.check(eng.lib.dposer_keypoint_guided_sampler(eng.h, _C.ptr(p.flat), _C.ptr(p.packed), _C.ptr(ws), C.byref(p.desc), _C.ptr(p.x), _C.ptr(p.x_mean),
+                                                    C.c_void_p(p.ts_host.data_ptr()), int(start_step), int(run_steps), core._handle(), mode, _C.ptr(na),
+                                                    _C.ptr(nb), _C.ptr(root), _C.ptr(tr), _C.ptr(jr), 1 if batched else 0, _C.ptr(kp), _C.ptr(conf),
+                                                    _C.ptr(rows_d), int(kp.shape[1]), _C.ptr(fo), _C.ptr(ce), float(sigma), float(z_near),
+                                                    JOINT_GUIDED_NORMS.index(norm), _C.ptr(p.nz), int(seed), _C.ptr(p.traj), int(traj_stride or 1),
+                                                    float(grad_step), _C.ptr(flag), _C.ptr(scratch), _C.ptr(eng.freq(dev, model._fourier_W())),
+                                                    _C.ptr(model.sigmas), B, _C.stream_ptr()),
+             "dposer_keypoint_guided_sampler")
+    bad = int(flag.item())                           # the call's one host read, after the loop
+    if bad != 2 ** 31 - 1:
+        raise ValueError("Consider reduce the value of parameter: grad_step={} (the gradient is not finite at loop index {})".format(grad_step, bad))
+    return p.traj, p.x, p.x_mean
+
+
+def keypoint_residual_sum(joints, keypoints, conf, rows, focal, center, sigma, z_near):
+    """s [B] of the keypoint-residual stage on posed joints ``joints`` [B, >= 22, 3] in torch, differentiable in ``joints`` -- the rule of
+    ``dposer_keypoint_guide_stage`` (include/dposer_hip.h): live iff c > 0 and Z > z_near, r = focal J_xy / Z - (k - centre),
+    s = sum_live c^2 (rho(ru) + rho(rv)) with rho = gmof (sigma <= 0: r^2).  Returns (s, live [B, n_obs])."""
+    idx = torch.arange(keypoints.shape[1], device=keypoints.device) if rows is None else torch.tensor(rows, dtype=torch.long, device=keypoints.device)
+    c = torch.ones(keypoints.shape[:2], dtype=joints.dtype, device=keypoints.device) if conf is None else conf
+    P = joints[:, idx]
+    Z = P[..., 2]
+    live = (c > 0) & (Z > z_near)                    # false for 0, negatives and NaN; a dead entry never enters a sum
+    Zs = torch.where(live, Z, torch.ones_like(Z))
+    k = torch.where(live[..., None], keypoints, torch.zeros_like(keypoints))
+    r = focal[:, None, None] * (P[..., :2] / Zs[..., None]) - (k - center[:, None, :])
+    r2 = r * r
+    rho = (sigma ** 2 * r2) / (sigma ** 2 + r2) if sigma > 0 else r2
+    c = torch.where(live, c, torch.zeros_like(c))
+    return (c * c * torch.where(live[..., None], rho, torch.zeros_like(rho)).sum(dim=2)).sum(dim=1), live
+
+
+def keypoint_guided_step(rsde, body_model, normalizer, x_t, t, z, kp, conf, rows, cam_t, center, focal, sigma, z_near, root_orient, betas, norm,
+                         grad_step):
+    """One step of DPS on observed 2D keypoints with torch autograd through the score function and ``fk_joints(grad="chain")`` -- what
+    ``dposer_keypoint_guided_sampler`` runs per loop index, for the models and SDEs it does not take.  Returns (y_hat, y_mean)."""
+    import contextlib
+    x_t = x_t.detach().requires_grad_()
+    dt = -1.0 / rsde.N
+    model = getattr(getattr(rsde, "_score_fn", None), "model", None)
+    only_x = model.input_grad_only() if hasattr(model, "input_grad_only") else contextlib.nullcontext()
+    with torch.enable_grad():
+        with only_x:
+            drift, diffusion, alpha, sigma_2, score = rsde.sde(x_t, t, None, None, guide=True)
+        y_mean = x_t.detach() + drift.detach() * dt
+        y_hat = y_mean + diffusion[:, None] * np.sqrt(-dt) * z
+        y0 = (x_t + sigma_2[:, None] * score) / alpha
+        joints = body_model.fk_joints(normalizer.offline_denormalize(y0), root_orient=root_orient, trans=cam_t, betas=betas, grad="chain")
+        s, _ = keypoint_residual_sum(joints, kp, conf, rows, focal, center, sigma, z_near)
+        if norm == "batch":
+            s = s.sum().reshape(1)
+        on = s > 0                                   # norm == 0: no guidance (sqrt has no gradient there)
+        total = torch.where(on, torch.sqrt(torch.where(on, s, torch.ones_like(s))), torch.zeros_like(s)).sum()
+        g = torch.autograd.grad(total, x_t)[0] if total.requires_grad else torch.zeros_like(y_hat)
+    if not torch.isfinite(g).all() or not torch.isfinite(s).all():
+        raise ValueError("Consider reduce the value of parameter: grad_step={}".format(grad_step))
+    return (y_hat - grad_step * g).detach(), y_mean.detach()
+
+
+def get_keypoint_guided_sampler(sde, shape, body_model, normalizer, focal_length=5000.0, sigma=100.0, z_near=0.1, grad_step=1.0, norm="sample",
+                                continuous=True, denoise=True, eps=1e-3, device="cuda"):
+    """DPS on observed 2D keypoints: the loop of ``get_joint_guided_sampler`` with a pinhole camera and SMPLify's robust reprojection
+    residual as the measurement -- a detector's keypoints.  Several calls (or a tiled batch) draw several bodies that reproject onto the
+    same keypoints and differ in what one view does not fix, depth above all.
+
+    ``sampler(model, keypoints2d, keypoints_conf=None, obs_joints=None, *, cam_t, camera_center, root_orient=None, betas=None, z=None,
+    start_step=0, traj_stride=1, noise=None, seed=None)`` returns ``(trajs [n, B, 63], x_mean if denoise else x)`` in the network's
+    normalised space.  ``keypoints2d`` [B, n_obs, 2] pixels; ``keypoints_conf`` [B, n_obs] or [n_obs]; ``obs_joints``: the n_obs distinct
+    tree joints in [0, 22) the columns observe (default 0 .. n_obs - 1; the vertex-selected extra joints of the 49-joint map are not
+    supported); ``cam_t`` [B, 3] the camera translation, added to the posed joints as SMPLify's ``transl=camera_t``; ``camera_center``
+    [B, 2]; ``focal_length`` a number or [B].  An entry counts iff its confidence is > 0 AND its joint lies in front of ``z_near`` (metres)
+    at that evaluation; what lies under a dead entry may be NaN.  The residual is ``focal X / Z - (k - centre)`` under the Geman-McClure
+    ``sigma`` (<= 0: none), weighted by the squared confidence.  ``norm``, ``noise``, ``seed``: as in ``get_joint_guided_sampler``.  A
+    ScoreModelFC on 63 inputs under continuous sub-VP / VP runs as ONE ``dposer_keypoint_guided_sampler`` call; everything else steps
+    ``keypoint_guided_step`` in Python."""
+    if norm not in JOINT_GUIDED_NORMS:
+        raise ValueError(f"unknown norm scope {norm!r}: expected one of {JOINT_GUIDED_NORMS}")
+    if len(shape) != 2 or int(shape[1]) != 63:
+        raise ValueError(f"the keypoint-guided sampler works on [B, 63] axis-angle body poses, got shape {tuple(shape)}")
+    if not float(z_near) > 0 or not np.isfinite(float(z_near)):
+        raise ValueError(f"z_near must be positive and finite, got {z_near}")
+    call_count = [0]
+
+    def keypoint_guided_sampler(model, keypoints2d, keypoints_conf=None, obs_joints=None, *, cam_t, camera_center, root_orient=None, betas=None, z=None,
+                                start_step=0, traj_stride=1, noise=None, seed=None):
+        B = int(shape[0])
+        kp, conf, rows, focal = _keypoint_guided_problem(keypoints2d, keypoints_conf, obs_joints, cam_t, camera_center, focal_length, sigma, z_near,
+                                                         root_orient, betas, B)
+        if z is not None and tuple(z.shape) != tuple(shape):
+            raise ValueError(f"z {tuple(z.shape)} does not have the sampler's shape {tuple(shape)}")
+        if not 0 <= start_step <= sde.N:
+            raise ValueError(f"start_step {start_step} outside [0, {sde.N}]")
+        n_run = sde.N - start_step
+        if noise is not None and tuple(noise.shape) != (n_run, 1) + tuple(shape):
+            raise ValueError(f"noise {tuple(noise.shape)}: expected {(n_run, 1) + tuple(shape)}")
+        x = sde.prior_sampling(shape).to(device) if z is None else z
+        _C.require_gpu(x, "sampler state")
+        _C.require_gpu(keypoints2d, "keypoint-guided sampler observation")
+        if fused_joint_guided_supported(sde, model, continuous):
+            call_count[0] += 1
+            if seed is None:
+                seed = (model._rng_seed * 7919 + call_count[0]) & 0xFFFFFFFFFFFF
+            was_training = model.training
+            model.eval()
+            try:
+                with torch.no_grad():
+                    trajs, x, x_mean = fused_keypoint_guided_sample(model, sde, x, torch.linspace(sde.T, eps, sde.N), body_model, normalizer, kp,
+                                                                    keypoints_conf=conf, obs_rows=rows, cam_t=cam_t, camera_center=camera_center,
+                                                                    focal=focal, sigma=sigma, z_near=z_near, root_orient=root_orient, betas=betas,
+                                                                    norm=norm, grad_step=grad_step, start_step=start_step, noise=noise, seed=seed,
+                                                                    traj_stride=traj_stride, continuous=continuous)
+            finally:
+                model.train(was_training)
+            if trajs is None:
+                trajs = x.new_empty((0,) + tuple(x.shape))
+            return trajs, (x_mean if denoise else x)
+        score_fn = mutils.get_score_fn(sde, model, train=False, continuous=continuous)
+        rsde = sde.reverse(score_fn, False)
+        timesteps = torch.linspace(sde.T, eps, sde.N, device=x.device)
+        f32 = lambda t: None if t is None else t.to(x.device).float()
+        kp_d, conf_d, cam_d, cen_d, foc_d, root_d, betas_d = f32(kp), f32(conf), f32(cam_t), f32(camera_center), f32(focal), f32(root_orient), f32(betas)
+        trajs, x_mean = [], x
+        for i in range(start_step, sde.N):
+            vec_t = torch.ones(shape[0], device=x.device) * timesteps[i]
+            zi = torch.randn_like(x) if noise is None else noise[i - start_step, 0]
+            x, x_mean = keypoint_guided_step(rsde, body_model, normalizer, x, vec_t, zi, kp_d, conf_d, rows, cam_d, cen_d, foc_d, float(sigma),
+                                             float(z_near), root_d, betas_d, norm, grad_step)
+            if traj_stride and (i - start_step + 1) % traj_stride == 0:
+                trajs.append(x)
+        trajs = torch.stack(trajs, dim=0) if trajs else x.new_empty((0,) + tuple(x.shape))
+        return trajs, (x_mean if denoise else x)
+
+    return keypoint_guided_sampler
+
+
 def get_ode_sampler(sde, shape, inverse_scaler, denoise=False, rtol=1e-5, atol=1e-5, method="RK45", eps=1e-3, device="cuda", driver=None,
                     n_steps=None):
     """Probability-flow ODE sampler (sampling.py:471-542): ``ode_sampler(model, z=None) -> (nfe, samples)``.

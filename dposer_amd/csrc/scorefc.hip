@@ -2165,38 +2165,36 @@ extern "C" int dposer_guided_sampler(dposer_scorefc_t h, const float* flat, cons
     return DPOSER_OK;
 }
 
-// DPS on observed 3D joints (include/dposer_hip.h has the contract): dposer_guided_sampler's loop with the joint-residual stage as the
-// measurement.  Per loop index: network with kept activations -> y0 rows -> dposer_joint_guide_stage (s, v) -> [batch scope: fixed-order sum of
-// s] -> upstream gradient from v -> dgrad-only backward -> update, which leaves the new state FT-tiled in w.xin.
+// DPS on observed 3D joints or 2D keypoints (include/dposer_hip.h has the contracts): dposer_guided_sampler's loop with a residual stage of
+// jointguide.hip as the measurement.  Per loop index: network with kept activations -> y0 rows -> the stage (s, v) -> [batch scope: fixed-order
+// sum of s] -> upstream gradient from v -> dgrad-only backward -> update, which leaves the new state FT-tiled in w.xin.
 //   scratch: the stage's | y0 [B][63] | v [B][63] | s [B]
-extern "C" int64_t dposer_joint_guided_scratch_bytes(int64_t batch) {
-    return batch < 1 ? 0 : dposer_joint_guide_stage_scratch_bytes(batch) + batch * (2 * 63 + 1) * (int64_t)sizeof(float);
-}
-extern "C" int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
-                                           float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, dposer_body_t body,
-                                           int32_t norm_mode, const float* norm_a, const float* norm_b, const float* root_orient, const float* transl,
-                                           const float* j_rest, int32_t j_rest_batched, const float* joints_obs, const float* joints_conf,
-                                           const int32_t* obs_rows, int32_t n_obs, int32_t norm_scope, const float* noise, uint64_t seed, float* traj,
-                                           int32_t traj_stride, float grad_step, int32_t* nonfinite_step, void* scratch, const float* freq,
-                                           const float* sigmas, int64_t B, void* stream) {
+// `entry` / `what` name the caller in the messages; obs_ok / obs_msg: its check of the observation block; stage(y0, s, v): its stage call.
+template <typename Stage>
+static int stage_guided_sampler(const char* entry, const char* what, dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_,
+                                const dposer_sde_desc* sde, float* x, float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps,
+                                dposer_body_t body, int32_t norm_mode, const float* norm_a, const float* norm_b, bool obs_ok, const char* obs_msg,
+                                int32_t n_obs, int32_t norm_scope, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, float grad_step,
+                                int32_t* nonfinite_step, void* scratch, int64_t stage_bytes, const float* freq, const float* sigmas, int64_t B,
+                                void* stream, Stage stage) {
     SharedT c;
-    DP_TRY(c.check(__func__, h, flat, packed_, ws_, B, stream));
-    DP_CHECK_ARG(sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
-    DP_CHECK_ARG(body && j_rest && joints_obs, "body, j_rest and joints_obs are required");
-    DP_CHECK_ARG(nonfinite_step, "nonfinite_step is required");
+    DP_TRY(c.check(entry, h, flat, packed_, ws_, B, stream));
+    DP_CHECK_ARG_AS(entry, sde && x && x_mean && timesteps_host && freq && sigmas, "null argument");
+    DP_CHECK_ARG_AS(entry, obs_ok, obs_msg);
+    DP_CHECK_ARG_AS(entry, nonfinite_step, "nonfinite_step is required");
     if (sde->kind == DPOSER_SDE_VE || sde->kind == DPOSER_SDE_VE_DISCRETE || sde->kind == DPOSER_SDE_VP_DISCRETE)
-        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, std::string(__func__) + ": the joint-guided sampler takes the continuous sub-VP and VP score functions");
-    DP_CHECK_ARG(sde->kind == DPOSER_SDE_SUBVP || sde->kind == DPOSER_SDE_VP, "unknown SDE kind");
+        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, std::string(entry) + ": the " + what + "-guided sampler takes the continuous sub-VP and VP score functions");
+    DP_CHECK_ARG_AS(entry, sde->kind == DPOSER_SDE_SUBVP || sde->kind == DPOSER_SDE_VP, "unknown SDE kind");
     if (h->D != 63)
-        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, std::string(__func__) + ": the network must work on 21 axis-angle joints (63 inputs); rot6d (126) is not supported");
-    DP_CHECK_ARG(sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
-    DP_CHECK_ARG(traj_stride >= 1, "traj_stride must be >= 1");
-    DP_CHECK_ARG(norm_scope == 0 || norm_scope == 1, "norm_scope must be 0 (batch) or 1 (sample)");
-    DP_CHECK_ARG(n_obs >= 1 && n_obs <= 22, "n_obs must be in 1..22");
-    DP_CHECK_ARG(norm_mode == 0 || ((norm_mode == 1 || norm_mode == 2) && norm_a && norm_b), "bad normaliser");
-    DP_CHECK_ARG(scratch && ((uintptr_t)scratch & 15) == 0, "scratch must be non-null and 16-byte aligned");
-    DP_CHECK_ARG(body_num_joints(body) > 22, "the body's tree must hold the 22 body joints first");
-    DP_CHECK_ARG(B < ((int64_t)1 << 31), "batch must be below 2^31");
+        return dposer_set_error(DPOSER_ERR_UNSUPPORTED, std::string(entry) + ": the network must work on 21 axis-angle joints (63 inputs); rot6d (126) is not supported");
+    DP_CHECK_ARG_AS(entry, sde->N >= 1 && start_step >= 0 && start_step <= sde->N, "bad step range");
+    DP_CHECK_ARG_AS(entry, traj_stride >= 1, "traj_stride must be >= 1");
+    DP_CHECK_ARG_AS(entry, norm_scope == 0 || norm_scope == 1, "norm_scope must be 0 (batch) or 1 (sample)");
+    DP_CHECK_ARG_AS(entry, n_obs >= 1 && n_obs <= 22, "n_obs must be in 1..22");
+    DP_CHECK_ARG_AS(entry, norm_mode == 0 || ((norm_mode == 1 || norm_mode == 2) && norm_a && norm_b), "bad normaliser");
+    DP_CHECK_ARG_AS(entry, scratch && ((uintptr_t)scratch & 15) == 0, "scratch must be non-null and 16-byte aligned");
+    DP_CHECK_ARG_AS(entry, body_num_joints(body) > 22, "the body's tree must hold the 22 body joints first");
+    DP_CHECK_ARG_AS(entry, B < ((int64_t)1 << 31), "batch must be below 2^31");
     const int n_run = steps_to_run(sde->N, start_step, n_steps);
     c.open(sde, DPOSER_WS_GUIDED, n_run);
     if (n_run == 0) return DPOSER_OK;
@@ -2205,7 +2203,7 @@ extern "C" int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat
     const char* packed = c.packed;
     DP_TRY(c.table(timesteps_host + start_step, n_run, freq));
     const int64_t BD = B * h->D;
-    float* y0 = reinterpret_cast<float*>(static_cast<char*>(scratch) + dposer_joint_guide_stage_scratch_bytes(B));
+    float* y0 = reinterpret_cast<float*>(static_cast<char*>(scratch) + stage_bytes);
     float* v = y0 + BD;
     float* s = v + BD;
     JointGuidedArgs ga{};
@@ -2220,14 +2218,55 @@ extern "C" int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat
         ga.traj = traj_slot(traj, i, traj_stride, BD);
         DP_TRY(forward_core_guided(h, flat, packed, w, i, B, st));
         DP_CHECK_HIP(launch_joint_guided_y0(ga, st));
-        DP_TRY(dposer_joint_guide_stage(body, y0, 63, norm_mode, norm_a, norm_b, root_orient, transl, j_rest, j_rest_batched, joints_obs, joints_conf,
-                                        obs_rows, n_obs, s, v, scratch, B, stream));
+        DP_TRY(stage(y0, s, v));
         if (norm_scope == 0) DP_CHECK_HIP(launch_sum_partials(s, (int)B, w.scalar, st));
         DP_CHECK_HIP(launch_joint_guided_dres(ga, st));
         DP_TRY(backward_core(h, flat, packed, w, B, false, 0, 0, nullptr, w.zbuf, nullptr, st));
         DP_CHECK_HIP(launch_joint_guided_update(ga, st));
     }
     return DPOSER_OK;
+}
+extern "C" int64_t dposer_joint_guided_scratch_bytes(int64_t batch) {
+    return batch < 1 ? 0 : dposer_joint_guide_stage_scratch_bytes(batch) + batch * (2 * 63 + 1) * (int64_t)sizeof(float);
+}
+extern "C" int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
+                                           float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, dposer_body_t body,
+                                           int32_t norm_mode, const float* norm_a, const float* norm_b, const float* root_orient, const float* transl,
+                                           const float* j_rest, int32_t j_rest_batched, const float* joints_obs, const float* joints_conf,
+                                           const int32_t* obs_rows, int32_t n_obs, int32_t norm_scope, const float* noise, uint64_t seed, float* traj,
+                                           int32_t traj_stride, float grad_step, int32_t* nonfinite_step, void* scratch, const float* freq,
+                                           const float* sigmas, int64_t B, void* stream) {
+    return stage_guided_sampler(__func__, "joint", h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, body, norm_mode, norm_a, norm_b,
+                                body && j_rest && joints_obs, "body, j_rest and joints_obs are required", n_obs, norm_scope, noise, seed, traj, traj_stride,
+                                grad_step, nonfinite_step, scratch, dposer_joint_guide_stage_scratch_bytes(B), freq, sigmas, B, stream,
+                                [&](const float* y0, float* s, float* v) {
+                                    return dposer_joint_guide_stage(body, y0, 63, norm_mode, norm_a, norm_b, root_orient, transl, j_rest, j_rest_batched,
+                                                                    joints_obs, joints_conf, obs_rows, n_obs, s, v, scratch, B, stream);
+                                });
+}
+
+// DPS on observed 2D keypoints: the same loop around dposer_keypoint_guide_stage
+extern "C" int64_t dposer_keypoint_guided_scratch_bytes(int64_t batch) {
+    return batch < 1 ? 0 : dposer_keypoint_guide_stage_scratch_bytes(batch) + batch * (2 * 63 + 1) * (int64_t)sizeof(float);
+}
+extern "C" int dposer_keypoint_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed_, void* ws_, const dposer_sde_desc* sde, float* x,
+                                              float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, dposer_body_t body,
+                                              int32_t norm_mode, const float* norm_a, const float* norm_b, const float* root_orient, const float* transl,
+                                              const float* j_rest, int32_t j_rest_batched, const float* keypoints, const float* keypoints_conf,
+                                              const int32_t* obs_rows, int32_t n_obs, const float* focal, const float* center, float sigma, float z_near,
+                                              int32_t norm_scope, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, float grad_step,
+                                              int32_t* nonfinite_step, void* scratch, const float* freq, const float* sigmas, int64_t B, void* stream) {
+    // (the stage repeats these two at every index; here they come before the first launch of the call)
+    DP_CHECK_ARG(z_near > 0.f && z_near <= 3.0e38f, "z_near must be positive and finite");
+    DP_CHECK_ARG(sigma <= 0.f || (sigma >= 1.0e-18f && sigma <= 1.0e18f), "sigma must be <= 0 (no robustifier) or in [1e-18, 1e18]: its square must be a normal float");
+    return stage_guided_sampler(__func__, "keypoint", h, flat, packed_, ws_, sde, x, x_mean, timesteps_host, start_step, n_steps, body, norm_mode, norm_a,
+                                norm_b, body && j_rest && keypoints && focal && center, "body, j_rest, keypoints, focal and center are required", n_obs,
+                                norm_scope, noise, seed, traj, traj_stride, grad_step, nonfinite_step, scratch, dposer_keypoint_guide_stage_scratch_bytes(B),
+                                freq, sigmas, B, stream, [&](const float* y0, float* s, float* v) {
+                                    return dposer_keypoint_guide_stage(body, y0, 63, norm_mode, norm_a, norm_b, root_orient, transl, j_rest, j_rest_batched,
+                                                                       keypoints, keypoints_conf, obs_rows, n_obs, focal, center, sigma, z_near, s, v,
+                                                                       scratch, B, stream);
+                                });
 }
 
 extern "C" int dposer_grad_sqnorm(const float* grad, int64_t n, float* scratch, void* stream) {

@@ -266,3 +266,94 @@ def sample_from_joints(model, sde, normalizer, body_model, joints3d, *, joints_c
             pe = pose_pair_errors(body_model, gt_poses.to(dev).float(), out["poses"], betas=betas)
             out["mpjpe"], out["mpvpe"] = pe["mpjpe"], pe["mpvpe"]
     return out
+
+
+def keypoint_residual_stage(body_model, normalizer, y0, keypoints2d, *, keypoints_conf=None, obs_joints=None, cam_t, camera_center, focal_length=5000.0,
+                            sigma=100.0, z_near=0.1, root_orient=None, betas=None):
+    """The measurement stage of guidance by observed 2D keypoints, for a batch of normalised poses: ``dposer_keypoint_guide_stage``, one
+    library call.  ``y0`` [B, 63] normalised body poses (axis-angle networks only); ``keypoints2d`` [B, n_obs, 2] pixels; ``keypoints_conf``
+    [B, n_obs] or [n_obs]; ``obs_joints``: the n_obs distinct body joints in [0, 22) the columns observe (default 0 .. n_obs - 1);
+    ``cam_t`` [B, 3] the camera translation (added to the posed joints, SMPLify's ``transl=camera_t``), ``camera_center`` [B, 2],
+    ``focal_length`` a number or [B]; ``root_orient`` [B, 3]; ``betas`` [B, n].  An entry counts iff its confidence is > 0 and its joint's
+    depth is > ``z_near``; what lies under a dead entry may be NaN.  Returns ``(s [B], v [B, 63])``: s = sum_live c^2 (rho(ru) + rho(rv)),
+    r = focal J_xy / J_z - (k - centre), rho the Geman-McClure function of ``sigma`` (<= 0: r^2), and v = 1/2 ds/dy0.  Shapes, ``obs_joints``
+    and the scalars are checked before any device work."""
+    from ..algorithms.advanced.sampling import _keypoint_guided_problem
+    from ._fused import normalizer_tables
+    if y0.dim() != 2 or y0.shape[1] != 63:
+        raise ValueError(f"y0 must be [B, 63] (21 axis-angle body joints; rot6d networks are not supported), got {list(y0.shape)}")
+    B = int(y0.shape[0])
+    kp, conf, rows, focal = _keypoint_guided_problem(keypoints2d, keypoints_conf, obs_joints, cam_t, camera_center, focal_length, sigma, z_near, root_orient,
+                                                     betas, B)
+    _C.require_gpu(y0, "y0")
+    dev = y0.device
+    core = body_model.bm
+    with torch.no_grad():
+        _, j_rest, batched = core.rest_shape(betas, None)
+    f32 = lambda t: None if t is None else t.detach().to(dev).contiguous().float()
+    y, kp, conf, root, tr, jr, fo, ce = f32(y0), f32(kp), f32(conf), f32(root_orient), f32(cam_t), f32(j_rest), f32(focal), f32(camera_center)
+    mode, na, nb = normalizer_tables(normalizer, y)
+    rows_d = None if rows is None else torch.tensor(rows, dtype=torch.int32, device=dev)
+    lib = _C.lib()
+    s = torch.empty(B, dtype=torch.float32, device=dev)
+    v = torch.empty(B, 63, dtype=torch.float32, device=dev)
+    scratch = torch.empty(lib.dposer_keypoint_guide_stage_scratch_bytes(B), dtype=torch.uint8, device=dev)
+    _C.check(lib.dposer_keypoint_guide_stage(core._handle(), _C.ptr(y), 63, mode, _C.ptr(na), _C.ptr(nb), _C.ptr(root), _C.ptr(tr), _C.ptr(jr),
+                                             1 if batched else 0, _C.ptr(kp), _C.ptr(conf), _C.ptr(rows_d), int(kp.shape[1]), _C.ptr(fo), _C.ptr(ce),
+                                             float(sigma), float(z_near), _C.ptr(s), _C.ptr(v), _C.ptr(scratch), B, _C.stream_ptr()),
+             "dposer_keypoint_guide_stage")
+    return s, v
+
+
+def sample_from_keypoints(model, sde, normalizer, body_model, keypoints2d, *, keypoints_conf=None, obs_joints=None, cam_t, camera_center,
+                          focal_length=5000.0, sigma=100.0, z_near=0.1, hypo=1, grad_step=1.0, norm="sample", gt_poses=None, root_orient=None, betas=None,
+                          continuous=True, eps=1e-3, noise=None, seed=None, z=None, start_step=0):
+    """``hypo`` plausible bodies for every set of observed 2D keypoints: DPS under the DPoser prior with the reprojected joints as the
+    measurement (``sampling.get_keypoint_guided_sampler``), all hypotheses in one batch.  Where SMPLify returns one body per image, this
+    returns several that reproject onto the same keypoints and differ in what one view leaves open.
+
+    ``keypoints2d`` [B, n_obs, 2] pixels (NaN allowed under a confidence that is not > 0), ``keypoints_conf`` [B, n_obs] or None,
+    ``obs_joints`` the observed tree joints in [0, 22) (default 0 .. n_obs - 1); ``cam_t`` [B, 3], ``camera_center`` [B, 2],
+    ``focal_length`` a number or [B]; ``root_orient`` [B, 3], ``betas`` [B, n].  The observation is tiled over the hypotheses (rows
+    b * hypo + k); ``noise`` [N - start_step, 1, B * hypo, 63] / ``z`` [B * hypo, 63] inject the draws and ``start_step`` enters the loop
+    late.  Returns a dict: ``poses`` [B, hypo, 63] axis-angle (de-normalised); ``reprojection_error`` [B, hypo]: the mean pixel distance
+    between the projected and the observed keypoints over the entries live at the final pose (confidence > 0 and depth > ``z_near``),
+    without the robustifier, NaN where there are none; ``depth_spread`` [B]: the standard deviation over the hypotheses of the mean depth
+    of the 22 joints, in metres (0 for ``hypo`` = 1) -- what a sampler shows and an optimiser cannot; and, with ``gt_poses`` [B, 63],
+    ``mpjpe`` / ``mpvpe`` [B]: the minimum over the hypotheses through ``utils.metric.pose_pair_errors``."""
+    from ..algorithms.advanced import sampling
+    from ..utils.metric import pose_pair_errors
+    if keypoints2d.dim() != 3 or keypoints2d.shape[2] != 2:
+        raise ValueError(f"keypoints2d must be [B, n_obs, 2], got {list(keypoints2d.shape)}")
+    if int(hypo) < 1:
+        raise ValueError(f"hypo must be >= 1, got {hypo}")
+    B, K = int(keypoints2d.shape[0]), int(hypo)
+    kp, conf, rows, focal = sampling._keypoint_guided_problem(keypoints2d, keypoints_conf, obs_joints, cam_t, camera_center, focal_length, sigma, z_near,
+                                                              root_orient, betas, B)                  # (host checks before any device work)
+    if gt_poses is not None and tuple(gt_poses.shape) != (B, 63):
+        raise ValueError(f"gt_poses must be [{B}, 63], got {list(gt_poses.shape)}")
+    tile = lambda t: None if t is None else t.repeat_interleave(K, dim=0)
+    dev = keypoints2d.device
+    fn = sampling.get_keypoint_guided_sampler(sde, (B * K, 63), body_model, normalizer, focal_length=tile(focal), sigma=sigma, z_near=z_near,
+                                              grad_step=grad_step, norm=norm, continuous=continuous, denoise=True, eps=eps, device=dev)
+    kp_t, conf_t, root_t, cam_tt, cen_t, betas_t, focal_t = tile(kp), tile(conf), tile(root_orient), tile(cam_t), tile(camera_center), tile(betas), tile(focal)
+    _, x = fn(model, kp_t, conf_t, rows, cam_t=cam_tt, camera_center=cen_t, root_orient=root_t, betas=betas_t, z=z, start_step=start_step, traj_stride=0,
+              noise=noise, seed=seed)
+    with torch.no_grad():
+        poses = normalizer.offline_denormalize(x)
+        joints = body_model.fk_joints(poses, root_orient=root_t, trans=cam_tt.to(dev).float(), betas=betas_t)[:, :22]
+        idx = torch.arange(kp_t.shape[1], device=dev) if rows is None else torch.tensor(rows, dtype=torch.long, device=dev)
+        P = joints[:, idx]
+        live = (torch.ones(kp_t.shape[:2], dtype=torch.bool, device=dev) if conf_t is None else conf_t > 0) & (P[..., 2] > z_near)
+        Zs = torch.where(live, P[..., 2], torch.ones_like(P[..., 2]))
+        proj = focal_t.to(dev)[:, None, None] * (P[..., :2] / Zs[..., None]) + cen_t.to(dev).float()[:, None, :]
+        d = proj - torch.where(live[..., None], kp_t.float(), torch.zeros_like(kp_t, dtype=torch.float32))
+        dist = torch.where(live, torch.sqrt((d * d).sum(dim=2)), torch.zeros_like(d[..., 0]))
+        cnt = live.sum(dim=1)
+        err = torch.where(cnt > 0, dist.sum(dim=1) / cnt.clamp_min(1), torch.full_like(dist[:, 0], float("nan")))
+        depth = joints[..., 2].mean(dim=1).reshape(B, K)
+        out = {"poses": poses.reshape(B, K, 63), "reprojection_error": err.reshape(B, K), "depth_spread": depth.std(dim=1, unbiased=False)}
+        if gt_poses is not None:
+            pe = pose_pair_errors(body_model, gt_poses.to(dev).float(), out["poses"], betas=betas)
+            out["mpjpe"], out["mpvpe"] = pe["mpjpe"], pe["mpvpe"]
+    return out

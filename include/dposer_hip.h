@@ -625,6 +625,54 @@ int dposer_joint_guided_sampler(dposer_scorefc_t h, const float* flat, const voi
                                 int32_t traj_stride, float grad_step, int32_t* nonfinite_step, void* scratch, const float* freq,
                                 const float* sigmas, int64_t B, void* stream);
 
+/* The keypoint-residual stage of a 2D-keypoint measurement on a normalised body pose: dposer_joint_guide_stage with a pinhole camera and
+ * SMPLify's robust reprojection residual (lib/body_model/fitting_losses.py:6-47 perspective_projection + gmof, :69-75 the weighted
+ * residual of body_fitting_loss) in place of the 3D distance.  body .. j_rest_batched, obs_rows, n_obs, s, v, scratch, batch, stream: the
+ * contract of dposer_joint_guide_stage, word for word.  transl [B,3] or NULL is the CAMERA translation: FK adds it to the posed joints,
+ * exactly as SMPLify passes transl = camera_t to the body model (perspective_projection never adds its `translation` argument, and the
+ * camera rotation is the identity: fitting_losses.py:69).  The camera and the observation:
+ *   keypoints [B, n_obs, 2] pixels;  keypoints_conf [B, n_obs] or NULL = 1;
+ *   focal  DEVICE [B]: one focal length per pose, pixels (a caller with one camera fills the vector);  center DEVICE [B, 2] pixels;
+ *   sigma: the Geman-McClure scale in pixels, <= 0 = no robustifier; a positive sigma outside [1e-18, 1e18] (its square is no normal float)
+ *     and NaN are refused;   z_near > 0, finite: the nearest depth that projects, metres.
+ * Per pose b and column j, with (X, Y, Z) = posed joint rows[j]:
+ *   LIVE iff c > 0 (false for 0, negatives and NaN) AND Z > z_near (false for NaN).  A dead entry's keypoint may be NaN or Inf and never
+ *     enters a sum.  A joint at or behind z_near is dead for this evaluation, in s and in v alike; it is not an error.
+ *   ru = focal (X / Z) - (k_u - center_u),  rv = focal (Y / Z) - (k_v - center_v): the centre is taken off the observation, not added to
+ *     the projection, so that no pair of numbers hundreds of pixels large is subtracted;
+ *   rho(r) = sigma^2 r^2 / (sigma^2 + r^2)  (gmof),  or r^2 for sigma <= 0;
+ *   s[b] = sum_live c^2 (rho(ru) + rho(rv))           [B]      (the weight is the reference's joints_conf ** 2, not the 3D stage's c)
+ *   v[b] = 1/2 d s[b] / d y0[b]                        [B, 63]: FK forward, residual and its gradient on the 22 posed joints (one lane per
+ *                                                      pose, zeros for unobserved rows, columns in ascending order), the reverse walk of
+ *                                                      dposer_fk_joints_backward, the normaliser's scale.  No live entry: s = 0, v = 0.
+ * The 22 tree joints only: the extra joints SMPLify reads from vertices (nose, eyes, ears, toes) are not observed here.
+ * fp32 throughout; the same inputs give the same bits.  data_dim must be 63: a rot6d network (126) returns DPOSER_ERR_UNSUPPORTED.
+ * scratch: caller-owned, >= dposer_keypoint_guide_stage_scratch_bytes(batch), 16-byte aligned.  Every argument is checked before the first
+ * launch; no allocation, no synchronisation. */
+int64_t dposer_keypoint_guide_stage_scratch_bytes(int64_t batch);
+int dposer_keypoint_guide_stage(dposer_body_t body, const float* y0, int32_t data_dim, int32_t norm_mode, const float* norm_a,
+                                const float* norm_b, const float* root_orient, const float* transl, const float* j_rest,
+                                int32_t j_rest_batched, const float* keypoints, const float* keypoints_conf, const int32_t* obs_rows,
+                                int32_t n_obs, const float* focal, const float* center, float sigma, float z_near, float* s, float* v,
+                                void* scratch, int64_t batch, void* stream);
+
+/* DPS on observed 2D keypoints, every step in one call: dposer_joint_guided_sampler's loop -- the same launches around the stage -- with
+ * dposer_keypoint_guide_stage as the measurement: K bodies that reproject onto the same keypoints and differ in depth.  Arguments: those
+ * of dposer_joint_guided_sampler with the keypoint stage's observation block (keypoints .. z_near) in place of joints_obs / joints_conf;
+ * norm_scope, trajectory slots, nonfinite_step (a NaN keypoint under a positive confidence raises it at its loop index), noise injection
+ * and the Philox stream are the same.  Liveness is decided anew at every index: a joint that y0 puts at or behind z_near does not guide
+ * that index.  scratch >= dposer_keypoint_guided_scratch_bytes(B) bytes, 16-byte aligned.  Continuous sub-VP and VP only, D = 63 only:
+ * everything else returns DPOSER_ERR_UNSUPPORTED.  Every argument is checked before anything is launched; no allocation, no
+ * synchronisation. */
+int64_t dposer_keypoint_guided_scratch_bytes(int64_t batch);
+int dposer_keypoint_guided_sampler(dposer_scorefc_t h, const float* flat, const void* packed, void* ws, const dposer_sde_desc* sde, float* x,
+                                   float* x_mean, const float* timesteps_host, int32_t start_step, int32_t n_steps, dposer_body_t body,
+                                   int32_t norm_mode, const float* norm_a, const float* norm_b, const float* root_orient, const float* transl,
+                                   const float* j_rest, int32_t j_rest_batched, const float* keypoints, const float* keypoints_conf,
+                                   const int32_t* obs_rows, int32_t n_obs, const float* focal, const float* center, float sigma, float z_near,
+                                   int32_t norm_scope, const float* noise, uint64_t seed, float* traj, int32_t traj_stride, float grad_step,
+                                   int32_t* nonfinite_step, void* scratch, const float* freq, const float* sigmas, int64_t B, void* stream);
+
 /* Linear blend skinning -- smplx/lbs.py lbs() + SMPLX.forward joint assembly, as called from
  * lib/body_model/body_model.py:75-103 (BodyModel.forward) and lib/body_model/smpl.py:67-77.
  *   posedirs_packed: dposer_lbs_pack_posedirs(posedirs [(J-1)*9, V*3]) (MFMA fragment order, fp32);
