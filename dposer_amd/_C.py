@@ -214,6 +214,7 @@ SIGNATURES = {
     "dposer_scorefc_packed_bytes": (i64, [vp, i32]),
     "dposer_scorefc_pack": (C.c_int, [vp, vp, vp, i32, vp]),
     "dposer_scorefc_workspace_bytes": (i64, [vp, i64, i32, i32]),
+    "dposer_scorefc_plan": (C.c_int, [vp, i64, i32, C.POINTER(i32)]),
     "dposer_scorefc_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dposer_scorefc_forward_train": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u32, vp]),
     "dposer_scorefc_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u32, vp]),

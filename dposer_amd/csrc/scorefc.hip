@@ -1721,6 +1721,31 @@ static int plan_wgrad_groups(const dposer_scorefc_s* h, const Ws& w, bool tr, in
 //                              (grouped)  one lane launch per layer group + that group's reductions and bucket events (data parallel);
 //                              (split-K)  per layer two split-K wgrad GEMMs + the bucket's reduction, optionally on the handle's second
 //                                         stream (fp32 mode, other widths, forced).
+// The forms the backward pass takes at one padded batch under the loaded tuning: decided here once, for backward_core and for
+// dposer_scorefc_plan (which reports them without launching anything).
+struct BwdForm {
+    bool tr, batched, two, silu_split;
+    int n_groups, grp_lo[MAX_L], grp_hi[MAX_L];
+    int gshape, tshape;      // tilings of the GroupNorm-backward dgrad and of the time-branch dgrad
+};
+static BwdForm plan_backward(const dposer_scorefc_s* h, const Ws& w, bool want_w, bool has_events, WgradBatchArgs& wb) {
+    BwdForm f;
+    const int64_t Bpad = w.Bpad;
+    f.tr = wgrad_tr_mode(h, Bpad);
+    f.batched = want_w && plan_batched_wgrad(h, w, f.tr, has_events, wb);      // (bf16x3: one lane launch per product term, the partial sets added by one reduction)
+    f.n_groups = (want_w && !f.batched && !h->x3) ? plan_wgrad_groups(h, w, f.tr, f.grp_lo, f.grp_hi) : 0;
+    f.two = want_w && !f.batched && f.n_groups == 0 && use_side_stream(Bpad);
+    f.gshape = gnbwd_shape(Bpad, h->gs, !h->f32);
+    f.tshape = main_shape(Bpad, h->E);
+    // time-branch dgrad, small batches: 40 tiles at 1280 samples, each walking K = L * H alone (36 us).  One k-split per layer segment fills the chip
+    // (12 us for the plain GEMM at 1280 samples, tools/tune_gemm.hip TUNE_SPLITK); k_silu_bwd_reduce adds the splits in layer order,
+    // applies act'(u) and keeps the column sums.  From ~4096 samples up the one launch is as fast: DPOSER_SILU_SPLIT_MAX.
+    // (bf16x3 has one GEMM per layer + the reduce pass at every batch size)
+    f.silu_split = h->x3 || (f.tr && (f.tshape == SHAPE_MID || f.tshape == SHAPE_SMALL) && w.dU_part && Bpad <= score_tuning().silu_split_max &&
+                             Bpad <= SILU_SPLIT_CAP && h->L <= GEMM_MAX_SEG && h->L <= 8);
+    return f;
+}
+
 static int backward_core(dposer_scorefc_s* h, const float* flat, const char* packed, Ws& w, int64_t B, bool dropout_on, uint64_t seed,
                          uint32_t step, float* flat_grad, float* dx, const BucketSink* sink, hipStream_t st,
                          const SumJob* loss_sum = nullptr, int dsm_cs_rows = 0) {
@@ -1728,18 +1753,18 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
     const int H = h->H, E = h->E, L = h->L, KBS = h->KBS, wk = h->wk;
     const int64_t Bpad = w.Bpad;
     const bool want_w = flat_grad != nullptr;
-    const bool tr = wgrad_tr_mode(h, Bpad);
     const bool has_events = sink != nullptr && sink->events != nullptr && sink->n_events > 0;
     WgradBatchArgs wb;
-    const bool batched = want_w && plan_batched_wgrad(h, w, tr, has_events, wb);      // (bf16x3: one lane launch per product term, the partial sets added by one reduction)
-    int grp_lo[MAX_L], grp_hi[MAX_L];
-    const int n_groups = (want_w && !batched && !h->x3) ? plan_wgrad_groups(h, w, tr, grp_lo, grp_hi) : 0;
+    const BwdForm form = plan_backward(h, w, want_w, has_events, wb);
+    const bool tr = form.tr, batched = form.batched, two = form.two;
+    const int n_groups = form.n_groups;
+    const int* grp_lo = form.grp_lo;
+    const int* grp_hi = form.grp_hi;
     // bf16x3: dres arrives from an elementwise kernel as fp32 fragment tiles
     DP_TRY(split_act(h, w.dres, w.p_dres, Bpad, h->Cp, st));
     const bool grouped = n_groups > 0;
     int cur_group = 0;
     bool front_a_done = false;
-    const bool two = want_w && !batched && !grouped && use_side_stream(Bpad);
     if (two) DP_TRY(ensure_side_stream(h));
     hipStream_t sw = two ? h->side : st;
     ReduceJobs rj;
@@ -1779,7 +1804,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
     } else if (loss_sum && loss_sum->n > 0) {
         DP_CHECK_HIP(launch_sum_partials(loss_sum->part, loss_sum->n, loss_sum->out, st));
     }
-    const int gshape = gnbwd_shape(Bpad, h->gs, !h->f32);
+    const int gshape = form.gshape;
     const int ws_rows = (int)(Bpad / (shape_st(gshape) * 32)) * shape_ws(gshape);   // partial rows written by the dgrad epilogue
     // GroupNorm affine / bias gradients of layer j from the partial sums its dgrad epilogue wrote
     auto add_layer_jobs = [&](int j) {
@@ -1875,7 +1900,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
     {
         // (at 8192 samples this is 256 workgroups of 128x128 with K = L*H = 5120 -- one per CU, latency-bound, 121 us; the
         //  128x32 tiling with 4x the workgroups was measured slower, 144 us)
-        const int shape = main_shape(Bpad, E);
+        const int shape = form.tshape;
         if (h->x3) {
             // bf16x3: one GEMM per layer (three plane segments against that layer's [E][3 H] matrix) into fp32 partials; k_silu_bwd_reduce adds
             // them in layer order, applies act'(u) and keeps the column sums -- the small-batch form of the bf16 mode, at every batch size
@@ -1897,10 +1922,7 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         g_next_flops = 2.0 * (double)B * E * L * H;
         GemmArgs g = gemm_args(packed + h->pk_wtT_all, L * H / KBS, E / (shape_ct(shape) * 32), (int)(Bpad / (shape_st(shape) * 32)));
         for (int l = 0; l < L; ++l) add_seg(g, w.dy[l], H / KBS);
-        // Small batches: 40 tiles at 1280 samples, each walking K = L * H alone (36 us).  One k-split per layer segment fills the chip
-        // (12 us for the plain GEMM at 1280 samples, tools/tune_gemm.hip TUNE_SPLITK); k_silu_bwd_reduce adds the splits in layer order,
-        // applies act'(u) and keeps the column sums.  From ~4096 samples up the one launch is as fast: DPOSER_SILU_SPLIT_MAX.
-        if (tr && (shape == SHAPE_MID || shape == SHAPE_SMALL) && w.dU_part && Bpad <= score_tuning().silu_split_max && Bpad <= SILU_SPLIT_CAP && L <= GEMM_MAX_SEG && L <= 8) {
+        if (form.silu_split) {      // one k-split per layer + the reduce pass (plan_backward has the conditions)
             g.ksplit = L;
             g.split_segments = 1;
             PartialFTParams pp;
@@ -1970,6 +1992,29 @@ static int backward_core(dposer_scorefc_s* h, const float* flat, const char* pac
         DP_CHECK_HIP(hipEventRecord(h->ev_join, sw));
         DP_CHECK_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
     }
+    return DPOSER_OK;
+}
+
+// Which tilings and launch forms a call with `batch` samples takes under the tuning currently loaded: the policy functions the launch
+// path itself calls, on a workspace laid out at address zero.  Host only.
+extern "C" int dposer_scorefc_plan(dposer_scorefc_t h, int64_t batch, int32_t with_bucket_events, int32_t plan[10]) {
+    DP_CHECK_ARG(h && plan, "dposer_scorefc_plan: NULL argument");
+    DP_CHECK_ARG(batch > 0, "dposer_scorefc_plan: batch must be positive");
+    g_act = h->d.activation;
+    Ws w;
+    layout_ws(h, batch, DPOSER_WS_TRAIN, 0, nullptr, w);
+    WgradBatchArgs wb;
+    const BwdForm f = plan_backward(h, w, true, with_bucket_events != 0, wb);
+    plan[0] = (int32_t)w.Bpad;
+    plan[1] = gn_shape(w.Bpad, h->H, h->gs, !h->f32);
+    plan[2] = f.gshape;
+    plan[3] = f.tshape;
+    plan[4] = final_shape(w.Bpad);
+    plan[5] = wgrad_shape(h->H, h->layer[h->L - 1].kin_pad, w.Bpad);
+    plan[6] = f.batched ? 1 : (f.n_groups > 0 ? 2 : 0);
+    plan[7] = f.n_groups;
+    plan[8] = f.silu_split ? 1 : 0;
+    plan[9] = f.two ? 1 : 0;
     return DPOSER_OK;
 }
 

@@ -115,6 +115,19 @@ int dposer_scorefc_debug_set_dropout_masks(dposer_scorefc_t h, const unsigned ch
 /* DPOSER_WS_GUIDED: the DPOSER_WS_TRAIN layout (every activation kept) followed by a time-bias table of n_steps rows (dposer_guided_sampler) */
 enum { DPOSER_WS_INFER = 0, DPOSER_WS_SHARED_T = 1, DPOSER_WS_TRAIN = 2, DPOSER_WS_GUIDED = 3 };
 int64_t dposer_scorefc_workspace_bytes(dposer_scorefc_t h, int64_t batch, int32_t mode, int32_t n_steps);
+/* Which GEMM tilings and launch forms a call with `batch` samples takes under the tuning currently loaded (dposer_scorefc_tuning_reload).
+ * Host only: no GPU is touched.  It runs the policy functions of the launch path itself, so a test that forces a tiling through the
+ * DPOSER_* switches can assert that the forcing took.  Tilings: 0 = 256x256, 1 = 128x128, 2 = 128x32, 3 = 64x128, 4 = 64x32,
+ * 5 = 128x64 (four waves), 6 = 128x64 (eight waves).
+ *   plan[0] padded batch                          plan[5] tiling of the hidden x hidden weight gradients (split-K form)
+ *   plan[1] GroupNorm layers, forward             plan[6] weight-gradient form: 0 split-K launches per layer, 1 one lane launch,
+ *   plan[2] GroupNorm-backward dgrad                      2 one lane launch per layer group
+ *   plan[3] time branch (forward and dgrad)       plan[7] number of layer groups (form 2; else 0)
+ *   plan[4] post_dense / dx / sampler step        plan[8] time-branch dgrad: 0 one launch, 1 one GEMM per layer + a reduce pass
+ *                                                 plan[9] parameter-gradient half on the second stream: 0 / 1
+ * with_bucket_events: the plan of dposer_dsm_loss_fwd_bwd_bucketed with bucket events (data parallel).  Returns 0, or -1 with
+ * dposer_last_error() set (NULL argument, batch <= 0). */
+int dposer_scorefc_plan(dposer_scorefc_t h, int64_t batch, int32_t with_bucket_events, int32_t plan[10]);
 
 /* ScoreModelFC.forward(batch, t) in eval mode -- model.py:141-196.
  *   x [B, D], labels [B] (what the reference calls `t` inside the model, i.e. t*999 from

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import bf16_ref as Q
+import score_plan as SP
 from gpu_common import DEV, t2n
 from helpers import _log_measured
 
@@ -47,6 +48,23 @@ def _model(case, dropout=0.0):
     return m, Q.case_inputs(c["seed"], c["B"], c["D"])
 
 
+def _force(tuning_env, m, case, env):
+    """Load the switches of a case and assert through ``dposer_scorefc_plan`` what they select.  ``score_plan.POLICY_BIG`` / ``POLICY_MID`` put the
+    256x256 / 128x128 tilings (and 64x128 for post_dense / dx) onto the small batches of the cases: the faithful oracle and its row rule
+    do not depend on the tiling, so the cases and their bounds are reused as they are."""
+    tuning_env(**env)
+    pl = SP.model_plan(m, Q.CASES[case]["B"])
+    if env.get("DPOSER_SMALL_TILE_MAX") == "0":
+        tile = SP.BIG if "DPOSER_BIG_MIN_BATCH" in env else SP.MID
+        assert (pl.gn, pl.gn_bwd, pl.time, pl.final, pl.wgrad) == (tile, tile, tile, SP.FINAL, tile), pl
+        assert pl.wgrad_form == (SP.SPLIT_K if env.get("DPOSER_WGRAD_BATCHED") == "0" else SP.ONE_LAUNCH), pl
+    return pl
+
+
+BIG_SPLITK = dict(SP.POLICY_BIG, DPOSER_WGRAD_BATCHED="0")
+MID_SPLITK = dict(SP.POLICY_MID, DPOSER_WGRAD_BATCHED="0")
+
+
 def _rows(got, case, name):
     return Q.check_rows(t2n(got), Q.reference(case)[name], Q.RECORD[case][name], log=_log_measured)
 
@@ -64,10 +82,11 @@ def _rows(got, case, name):
     ("fwd_b1100", {"DPOSER_FINAL_SMALL_MAX": "0"}),            # post_dense on the 64x128 tiling
     ("fwd_b200_d126", {}), ("fwd_b1100_d126", {}),             # rot6d: D = 126, two 64-channel output blocks
     ("fwd_b200_2blk", {}), ("fwd_b2304_2blk", {}),             # the shipped depth (residual input from layer 2 on)
+    ("fwd_b200", SP.POLICY_BIG), ("fwd_b200", SP.POLICY_MID),  # 256 padded samples on one 256x256 tile / two 128x128 tiles, post_dense on 64x128
 ])
 def test_forward_eval_rows_vs_faithful_oracle(case, env, tuning_env):
-    tuning_env(**env)
     m, (x, t, _) = _model(case)
+    _force(tuning_env, m, case, env)
     with torch.no_grad():
         out = m(_dev(x), _dev(t) * 999)
     _rows(out, case, "out")      # measured: clean share 0.69 ... 0.83 (p_ref 0.75 ... 0.88), largest flipped row 1.6e-3 ... 3.7e-3
@@ -86,9 +105,13 @@ def test_one_row_batch_carries_the_bits_of_its_row():
 # ------------------------------------------------------------------------------------------------
 # forward, train form: in-kernel Philox dropout, 1 / (1 - p) folded into the sigmoid's reciprocal
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["drop01_b200", "drop05_b200", "drop01_b1100", "drop05_b1100"])
-def test_forward_train_dropout_rows_vs_faithful_oracle(case):
+@pytest.mark.parametrize("case,env", [pytest.param(c, {}, id=c) for c in ("drop01_b200", "drop05_b200", "drop01_b1100", "drop05_b1100")] + [
+    # the Philox draw of (seed, step, sample, channel) inside the training epilogues of the 256x256 / 128x128 tilings
+    pytest.param("drop01_b200", SP.POLICY_BIG, id="drop01_b200-BIG"), pytest.param("drop05_b200", SP.POLICY_BIG, id="drop05_b200-BIG"),
+    pytest.param("drop01_b200", SP.POLICY_MID, id="drop01_b200-MID"), pytest.param("drop05_b200", SP.POLICY_MID, id="drop05_b200-MID")])
+def test_forward_train_dropout_rows_vs_faithful_oracle(case, env, tuning_env):
     m, (x, t, _) = _model(case, dropout=Q.CASES[case]["drop_p"])
+    _force(tuning_env, m, case, env)
     m.train()
     m._rng_seed, m._rng_step = Q.DROPOUT_RNG_SEED, Q.DROPOUT_RNG_STEP - 1      # the forward below draws at (seed, step 1): the oracle's masks
     with torch.no_grad():
@@ -169,6 +192,11 @@ def test_autograd_rows_vs_faithful_oracle(case):
     ("wgrad_b512", {}), ("wgrad_b1100", {}),                   # the default path: one lane launch for all 256x256 weight-gradient tiles
     ("wgrad_b2304", {"DPOSER_WGRAD_BATCHED": "0", "DPOSER_WGRAD_BIG": "1", "DPOSER_GNBWD_BIG": "1"}),   # split-K 256x256 wgrads, 256x256 EpiGNBwd
     ("wgrad_b512_tr0", {"DPOSER_WGRAD_TR": "0"}),              # wgrads on transposed operand copies
+    # 512 samples on the 128x128 tilings: the time-branch dgrad keeps its k-split form (``wgrad_b512``)
+    ("wgrad_b512", SP.POLICY_MID), ("wgrad_b512", MID_SPLITK),
+    # ... and on the 256x256 tilings, which have the one-launch form only: the inputs of ``wgrad_b512`` with the bias gradient of
+    # shared_time_embed summed before the store, which is the reference ``wgrad_b512_tr0`` holds
+    ("wgrad_b512_tr0", SP.POLICY_BIG), ("wgrad_b512_tr0", BIG_SPLITK),
 ])
 def test_parameter_gradients_over_clean_rows_vs_faithful_oracle(case, env, tuning_env):
     """Rows are independent in the dgrad and the library has no atomics.  Pass 1 finds the rows S that are clean in out and in x.grad (on
@@ -179,8 +207,9 @@ def test_parameter_gradients_over_clean_rows_vs_faithful_oracle(case, env, tunin
     errors (``bf16_ref.param_grad_bounds`` says why: an x_hat flip that x.grad cannot show).
     Measured (GPU / reference, rel-L2): matrices 1.0e-7 ... 6.5e-7 / 1.6e-7 ... 6.6e-7, their tiles 2.5e-7 ... 4.7e-6 / 5.1e-7 ... 4.7e-6;
     shared_time_embed 7.9e-6 ... 3.2e-5 / 1.1e-5 ... 1.3e-5; layer vectors at most 6.2e-6."""
-    tuning_env(**env)
     m, (x, t, g) = _model(case)
+    pl = _force(tuning_env, m, case, env)
+    assert pl.time_split == (1 if Q.CASES[case].get("se_bias_stored", True) else 0), pl      # which of the two forms the reference of the case restates
 
     def run(gg):
         for q in m.parameters():

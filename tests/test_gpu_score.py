@@ -821,21 +821,38 @@ def test_integration_md_ctypes_stub_runs():
 
 
 @pytest.mark.parametrize("env", [
-    {"DPOSER_GNBWD_BIG": "1", "DPOSER_WGRAD_BIG": "1", "DPOSER_BIG_MIN_BATCH": "256", "DPOSER_WGRAD_BATCHED": "0"},      # 256x256 tilings from 256 samples up
-    {"DPOSER_GNBWD_BIG": "0", "DPOSER_WGRAD_BIG": "0", "DPOSER_WGRAD_STREAM": "0", "DPOSER_WGRAD_BATCHED": "0"},          # 128x128 everywhere, single stream
+    # 256x256 tilings from 256 samples up (DPOSER_SMALL_TILE_MAX / DPOSER_FINAL_SMALL_MAX = 0: nothing keeps a small batch on 128x32 / 64x32)
+    {"DPOSER_GNBWD_BIG": "1", "DPOSER_WGRAD_BIG": "1", "DPOSER_BIG_MIN_BATCH": "256", "DPOSER_WGRAD_BATCHED": "0",
+     "DPOSER_SMALL_TILE_MAX": "0", "DPOSER_FINAL_SMALL_MAX": "0"},
+    # 128x128 everywhere, single stream
+    {"DPOSER_GNBWD_BIG": "0", "DPOSER_WGRAD_BIG": "0", "DPOSER_WGRAD_STREAM": "0", "DPOSER_WGRAD_BATCHED": "0",
+     "DPOSER_SMALL_TILE_MAX": "0", "DPOSER_FINAL_SMALL_MAX": "0"},
     {"DPOSER_WGRAD_TR": "0"},                                                                # bf16 wgrads on transposed copies
     {"DPOSER_WGRAD_STREAM": "1", "DPOSER_WGRAD_BATCHED": "0"},                                                  # wgrads on the second stream (default 8192..16384)
     {"DPOSER_WGRAD_BATCHED": "1"},                                                           # all 256x256 wgrad tiles in one launch (the single-GPU default)
 ])
-def test_alternative_tilings_and_streams_keep_parity(env):
+def test_alternative_tilings_and_streams_keep_parity(env, tuning_env):
     """The tiling / stream policy depends on the batch size (256x256 GroupNorm-backward and wgrad tiles from 32768 samples,
     second stream up to 16384).  The policies are read once per process, so the gradient-parity tests are re-run in a child
-    process with each policy forced onto the small batches the oracle can check."""
+    process with each policy forced onto the small batches the oracle can check.  That the first two environments force the tiling
+    they name is asserted here, through dposer_scorefc_plan, before the child starts."""
     import os
     import subprocess
     import sys
     if os.environ.get("DPOSER_TILING_CHILD"):
         pytest.skip("child process")
+    if "DPOSER_SMALL_TILE_MAX" in env:
+        import score_plan as SP
+        from dposer_amd import _C
+        tile = SP.BIG if env["DPOSER_GNBWD_BIG"] == "1" else SP.MID
+        tuning_env(**env)
+        for prec in ("fp32", "bf16", "bf16x3"):
+            h = SP.make_handle(1024, prec)
+            try:
+                assert SP.plan(h, 1000)[:8] == (1024, tile, tile, tile, SP.FINAL, tile, SP.SPLIT_K, 0), (prec, SP.plan(h, 1000))
+                assert SP.plan(h, 65)[:5] == (128, SP.MID, SP.MID, SP.MID, SP.FINAL), (prec, SP.plan(h, 65))      # (128 samples: no 256-row tile)
+            finally:
+                _C.lib().dposer_scorefc_destroy(h)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     child_env = dict(os.environ, DPOSER_TILING_CHILD="1", **env)
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_score.py"), "-m", "gpu", "-q", "-x", "-k",
@@ -1023,11 +1040,11 @@ def test_vp_sde_fused_paths_vs_oracle():
     (1, 512, 21, 3, True, 1024, 200), (3, 256, 21, 3, True, 1024, 200), (1, 128, 21, 3, True, 1024, 200), (2, 512, 16, 4, True, 1024, 200),
     (2, 512, 32, 4, False, 1024, 200), (2, 384, 40, 5, True, 1024, 200), (2, 512, 1, 3, True, 1024, 200), (2, 512, 50, 3, True, 1024, 200),
     (2, 512, 55, 6, True, 1024, 200),
-    # hidden_dim 512 / 2048: GroupNorm(32, H) groups of 16 / 64 channels (generic epilogues), on the 128x128 (B = 200 -> 256 rows) and
-    # the 128x32 tiling (B = 150 -> 192 rows)
+    # hidden_dim 512 / 2048: GroupNorm(32, H) groups of 16 / 64 channels (generic epilogues), on the 128x128 (B = 200 -> 256 rows, under
+    # DPOSER_SMALL_TILE_MAX=0) and the 128x32 tiling (B = 150 -> 192 rows, which 128 does not divide)
     (2, 512, 21, 3, True, 512, 200), (2, 512, 21, 3, True, 512, 150), (2, 256, 21, 6, True, 2048, 200), (1, 512, 21, 3, True, 2048, 150)])
 @pytest.mark.parametrize("prec", ["fp32", "bf16x3"])
-def test_other_model_configurations_vs_oracle(n_blocks, E, n_poses, pose_dim, sbs, H, B, prec):
+def test_other_model_configurations_vs_oracle(n_blocks, E, n_poses, pose_dim, sbs, H, B, prec, tuning_env):
     """ScoreModelFC configurations other than the shipped one (2 blocks, embed 512, D = 63, hidden 1024, scale_by_sigma): depth
     (residual-carry logic, bucket layout), embedding width, hidden width (GroupNorm group size), data dimensions that are / are
     not multiples of the 64-column padding (64, 128, 150, 200, 330, 3) and scale_by_sigma off.  Forward, sampler step and all
@@ -1049,6 +1066,13 @@ def test_other_model_configurations_vs_oracle(n_blocks, E, n_poses, pose_dim, sb
     p = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
     p["sigmas"] = R.sigma_table()
     assert len(m._engine().grad_buckets) == 2 + 2 * n_blocks          # layers L-1..1, front A, front B
+    if H != 1024:
+        # the generic-group epilogues take the 128-wide tilings only; up to 2048 samples the default policy keeps every batch on 128x32, so
+        # 128x128 -- what they get above -- is forced here, and the plan says whether it was
+        import score_plan as SP
+        tuning_env(DPOSER_SMALL_TILE_MAX="0")
+        want = SP.MID if B == 200 else SP.SMALL
+        assert SP.model_plan(m, B)[:4] == ((B + 63) // 64 * 64, want, want, want), SP.model_plan(m, B)
     rs = np.random.RandomState(n_blocks)
     x = rs.standard_normal((B, D)).astype(np.float32)
     t = rs.uniform(1e-3, 1.0, B).astype(np.float32)
@@ -1490,28 +1514,41 @@ def test_ve_probability_flow_ode_on_the_fused_right_hand_side(monkeypatch):
 
 @pytest.mark.parametrize("act", ["elu", "relu", "lrelu"])
 @pytest.mark.parametrize("prec,tol,tol_g", [("fp32", 2e-5, 2e-4), ("bf16", 1e-2, 1e-2), ("bf16x3", 2e-5, 2e-4)])      # bf16x3 (round 6): fp32 tolerances on the bf16 pipe
-def test_other_activations_vs_reference_golden(act, prec, tol, tol_g):
+def test_other_activations_vs_reference_golden(act, prec, tol, tol_g, tuning_env):
     """config.model.nonlinearity = elu / relu / lrelu (model.py:54-66 get_act): forward, DSM loss and every parameter gradient of
     the fused training path against g19 (the reference itself), through the runtime-activation epilogues of the 128-wide
-    tilings -- at a ragged batch (128 x 32 tiling) and, replicated 8 x, at a batch the 128 x 128 tiling takes."""
+    tilings -- at a ragged batch (128 x 32 tiling) and, replicated 16 x under DPOSER_SMALL_TILE_MAX=0, at a batch the 128 x 128 tiling
+    takes (384 samples; the default policy has it from 2048 samples up).  The mean over 16 copies of the batch is the mean over the
+    batch: the replicated training step has the golden's loss and gradients."""
+    import score_plan as SP
     g = load("g19_activations")
     cfg, m, p = make_model(int(g["seed"]), precision=prec, dropout=0.0, nonlinearity=act)
     batch, t = _dev(g["batch"]), _dev(g["t"])
+    tt = _dev(g["u"]) * (1.0 - 1e-5) + 1e-5
+    assert SP.model_plan(m, batch.shape[0])[1:4] == (SP.SMALL, SP.SMALL, SP.SMALL)
     with torch.no_grad():
         out = m(batch, t * 999)
-        out8 = m(batch.repeat(16, 1), (t * 999).repeat(16))            # 384 samples: 128 x 128 tiles
     assert rel_err(t2n(out), g[f"{act}_model"]) < tol
-    assert rel_err(t2n(out8[:24]), g[f"{act}_model"]) < tol
-    tt = _dev(g["u"]) * (1.0 - 1e-5) + 1e-5
-    loss, fg = _fused_grad(m, batch, tt, _dev(g["z"]))
-    assert abs(loss - float(g[f"{act}_loss"])) / float(g[f"{act}_loss"]) < (2e-3 if prec == "bf16" else 1e-4)
-    worst = 0.0
-    for (name, prm), off in zip(m.named_parameters(), m._offsets):
-        ref = g[f"{act}_grad/{name}"]
-        if ref.shape[0] > 1:
-            worst = max(worst, rel_err(probe(name, fg[off:off + prm.numel()].reshape(prm.shape)), ref))
-    # (relu / lrelu have a step derivative: a bf16-rounded pre-activation next to zero flips the gate, measured 1.2e-2)
-    assert worst < (3 * tol_g if (prec == "bf16" and act != "elu") else tol_g), worst
+
+    def check_step(loss, fg):
+        assert abs(loss - float(g[f"{act}_loss"])) / float(g[f"{act}_loss"]) < (2e-3 if prec == "bf16" else 1e-4)
+        worst = 0.0
+        for (name, prm), off in zip(m.named_parameters(), m._offsets):
+            ref = g[f"{act}_grad/{name}"]
+            if ref.shape[0] > 1:
+                worst = max(worst, rel_err(probe(name, fg[off:off + prm.numel()].reshape(prm.shape)), ref))
+        # (relu / lrelu have a step derivative: a bf16-rounded pre-activation next to zero flips the gate, measured 1.2e-2)
+        assert worst < (3 * tol_g if (prec == "bf16" and act != "elu") else tol_g), worst
+
+    check_step(*_fused_grad(m, batch, tt, _dev(g["z"])))
+    tuning_env(DPOSER_SMALL_TILE_MAX="0")
+    n = 16 * batch.shape[0]                                              # 384 samples: 128 x 128 tiles
+    assert SP.model_plan(m, n)[:4] == (384, SP.MID, SP.MID, SP.MID), SP.model_plan(m, n)
+    with torch.no_grad():
+        out16 = m(batch.repeat(16, 1), (t * 999).repeat(16))
+    assert rel_err(t2n(out16[:24]), g[f"{act}_model"]) < tol
+    assert rel_err(t2n(out16[-24:]), g[f"{act}_model"]) < tol
+    check_step(*_fused_grad(m, batch.repeat(16, 1), tt.repeat(16), _dev(g["z"]).repeat(16, 1)))
 
 
 def test_fused_adam_weight_decay_follows_torch():
